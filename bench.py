@@ -13,6 +13,12 @@ Hough voting (training mode: 9 rows per maximum + pose targets from planted grou
 ROI pooling -> fc6/7/8 + tanh -> hard_label + average_distance_loss on those rows -> all-gather of
 the fixed-size detection buffer -> D2H -> host NMS / pose assembly.
 
+A plain run sets up, warms up (W steps, then --prewarm-seconds of untimed load), times K steps and prints the
+line (`value`, `ms_per_step`, ...). `--full` adds everything else the benchmark measures or checks: the cold
+region, the --repeats spread, the serial re-run check, per-kernel timing and rooflines, the all-gather timing,
+`secondary` (configs[1] / configs[4]) and the CPU baseline. `--dump-outputs DIR` writes the last timed step's
+outputs as .npy files, so that two builds can be compared on the same seeded inputs.
+
   --config linemod   BASELINE configs[4]: 960x1280, LINEMOD 13 objects (C = 14), batch 4
   --batch 1 --latency   BASELINE configs[1]-style per-frame latency (p50 / p99), COLOR or RGBD
   --dry-run          distributed plumbing only (gloo, CPU): used by tests/test_bench_launch.py
@@ -30,6 +36,7 @@ sys.path.insert(0, ROOT)
 FP32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: dense fp32 matrix peak
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_ACHIEVABLE_GBPS = 6290.0    # ... measured float4 copy
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs: all arrays together (headers and manifest.json stay under 64 MB)
 
 
 def parse_args(argv=None):
@@ -72,9 +79,9 @@ def parse_args(argv=None):
                     help="A/B: conv1_1 + conv1_2's input transform and conv1_2 as the two round-3 kernels instead of the fused one")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the short configs[1] (batch-1 latency) and configs[4] (LINEMOD 1280x960 + backproject) runs whose "
-                         "summaries the default single-GPU invocation appends under `secondary`")
+                         "summaries a --full single-GPU invocation appends under `secondary`")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps run back to back: the FIRST is `value` / `ms_per_step` (the driver's contract, as in "
+                    help="with --full: timed regions of --steps steps run back to back: the FIRST is `value` / `ms_per_step` (the contract, as in "
                          "every earlier round); all of them give value_median / value_min / value_max, so one run says whether a 2 %% "
                          "change is a change (VERDICT r5 #3: five boxes read 793-827 on one build)")
     ap.add_argument("--nbuf", type=int, default=2, help="distinct synthetic batches cycled through")
@@ -92,6 +99,15 @@ def parse_args(argv=None):
                     help="every rank computes on cuda:0 (RCCL refuses two ranks on one device: use --backend gloo)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: launch / rendezvous / collective / JSON plumbing on gloo")
     ap.add_argument("--master-port", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the cold region, the --repeats regions, the serial re-run check "
+                         "(outputs_equal_serial), per-kernel event timing and the rooflines built on it, the all-gather timing, "
+                         "`secondary` and the CPU baseline. Without it a run sets up, warms up (W steps + the pre-warm), times the "
+                         "K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32: "
+                         "the detections as gathered, the rois / poses after host NMS, the label map, and with the backprojecting "
+                         "layer a fixed seeded sample of its voxel output; %d MiB at most in all" % (DUMP_BUDGET_BYTES >> 20))
     a = ap.parse_args(argv)
     # PCNN_BENCH_INPUTS = raw | resident | pinned: the frame hand-over of a line whose command is not ours to change (the driver's
     # `bench.py --gpus 8 --steps K --warmup W`): raw = --raw-inputs (24.6 MB per step and rank instead of 118), resident =
@@ -214,6 +230,41 @@ def per_rank_fields(rank_elapsed, steps, h2d_bytes):
     return out
 
 
+def last_step_outputs(last):
+    """What a caller of the timed path holds after its last step: the detection rows as gathered (global frame indices),
+    the rois / poses after host NMS, the step's label map and, with the backprojecting layer, its voxel output."""
+    outs = {"detections": last["flat"], "rois": last["rois"], "poses": last["poses"], "labels": last["det"].label_2d}
+    if last.get("backproject") is not None:
+        outs["backproject"] = last["backproject"]
+    return outs
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, small=1 << 20, seed=0):
+    """out_dir/<name>.npy in float32, `budget` bytes in all. Arrays of at most `small` bytes are written whole; the larger
+    ones share what is left, and one that exceeds its share is cut to a fixed seeded sample of its flattened elements
+    (the same indices in every run of the same shape). out_dir/manifest.json says which."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    numel = {k: int(v.numel() if torch.is_tensor(v) else np.asarray(v).size) for k, v in arrays.items()}
+    large = [k for k in arrays if 4 * numel[k] > small]
+    share = (budget - sum(4 * numel[k] for k in arrays if k not in large)) // max(1, len(large))
+    manifest = {}
+    for name, v in arrays.items():
+        t = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+        if 4 * numel[name] > share and name in large:
+            k = share // 4
+            idx = np.sort(np.random.default_rng(seed).integers(0, numel[name], k))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            entry["sample"] = {"elements": k, "of": numel[name], "indices": "sorted np.random.default_rng(%d).integers(0, %d, %d) "
+                               "into the flattened array" % (seed, numel[name], k)}
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+        manifest[name] = entry
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+
+
 def make_host_inputs(first, B, H, W, C, input_format, nbuf, extents, K, train, raw=False):
     """nbuf distinct synthetic batches: image blobs as pinned host tensors (what feed_dict holds in
     lib/fcn/test.py:151-170), the planted 1/8-resolution scene and its gt poses as numpy."""
@@ -311,7 +362,7 @@ def secondary_configs(timeout=150):
     }
     out = {}
     for name, flags in runs.items():
-        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--no-cpu-baseline", "--no-secondary"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ["--full", "--no-cpu-baseline", "--no-secondary"]
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, text=True)
@@ -486,11 +537,14 @@ def main(argv=None):
                     if gslots is not None:
                         upload(k)     # a memcpy node: pinned host buffer k -> device slot k
                     d = step(data, data_p, k)
-                    return d.rows, d.count, d.label_2d, net.get_output("poses_weight"), d.packed
+                    return (d.rows, d.count, d.label_2d, net.get_output("poses_weight"), d.packed) + ((last["backproject"],) if bp is not None else ())
                 graphs[k] = pipeline.GraphedStep(fn, warmup=1, device=dev)
-            rows, count, label_2d, pw, packed_ = graphs[k].replay()
+            outs = graphs[k].replay()
+            rows, count, label_2d, pw, packed_ = outs[:5]
             det = fcn.Detections(rows, count, label_2d, packed_)
             last["poses_weight"] = pw
+            if bp is not None:
+                last["backproject"] = outs[5]
         else:
             if gslots is not None:
                 upload(k)
@@ -514,7 +568,7 @@ def main(argv=None):
         if last.get("record") is not None:
             last["record"].append((ticket_batch[ticket], flat))   # (collect() already copied out of the pinned slot)
         rois, poses = fcn.finalize_batch(flat, flat.shape[0])
-        last["rois"] = rois
+        last["rois"], last["poses"], last["flat"] = rois, poses, flat
         if flat.shape[0]:   # detections carry GLOBAL frame indices (rank * B + local): whose frames reached this rank?
             last["ranks_seen"] = max(last.get("ranks_seen", 0), len(set((flat[:, 0] // B).astype(int).tolist())))
         return rois.shape[0]
@@ -583,55 +637,63 @@ def main(argv=None):
 
     lat = None
     with torch.no_grad():
-        # (1) the contract as written, on a cold process: W untimed warm-up steps (MIOpen find, library
-        # handles, allocator pools), then K timed steps -> value_cold
+        # (1) W untimed warm-up steps (MIOpen find, library handles, allocator pools); with --full then K timed
+        # steps on the cold process -> value_cold
         run(a.warmup)
         torch.cuda.synchronize()
         if a.graph:
             last["graph_ready"] = True      # everything is warm: from here on the step is a hipGraph replay
             run(2 * len(host))              # (captures one graph per device slot, untimed)
             torch.cuda.synchronize()
-        elapsed_cold, _ = timed(a.steps)
+        if a.full:
+            elapsed_cold, _ = timed(a.steps)
         # (2) the steady state a throughput job runs in: under sustained load the GPU's clocks keep rising
         # for several seconds (measured round 1: 962 / 1023 / 1132 frames/s after 0 / 2 / 8 s). Untimed.
         t_pre = time.perf_counter()
         while time.perf_counter() - t_pre < a.prewarm_seconds:
             run(4)
             torch.cuda.synchronize()
+        # the headline region starts on host batch 0 whatever ran before it (the pre-warm's length is a matter of time):
+        # the same arguments time, and --dump-outputs writes, the same batches in every run
+        run(-seq["i"] % len(host))
+        torch.cuda.synchronize()
         sep_profile = a.graph or len(streams) > 1
-        if not sep_profile:
-            _lib.profile_enable(True)   # HIP events around every library kernel, on the launch stream
-            net.conv_timing = []        # ... and around every remaining framework convolution / GEMM of the trunk
-        last["record"] = []       # the timed run's own detections, as the host received them (7 KB per step, already copied)
+        if a.full:
+            if not sep_profile:
+                _lib.profile_enable(True)   # HIP events around every library kernel, on the launch stream
+                net.conv_timing = []        # ... and around every remaining framework convolution / GEMM of the trunk
+            last["record"] = []       # the timed run's own detections, as the host received them (7 KB per step, already copied)
         first_timed = seq["i"]
         elapsed, ndet = timed(a.steps)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, last_step_outputs(last))
         host_launch_ms = 1000.0 * last["host_launch_s"] / a.steps
         rank_elapsed = pdist.gather_over_ranks(last["local_elapsed"], dev)   # the headline region, rank by rank
-        equal_serial = check_equal_serial(first_timed)
-        if sep_profile:
-            # per-kernel events cannot be recorded inside a graph replay, and with two streams a kernel's
-            # event pair also spans whatever the other stream ran in between: time the same kernels once
-            # more, eagerly on one stream
-            last["graph_ready"] = False
-            multi["on"] = False
-            net.conv_timing = []
-            _lib.profile_enable(True)
-            run(a.steps)
-            torch.cuda.synchronize()
-            multi["on"] = len(streams) > 1
-        kern = _lib.profile_report()
-        _lib.profile_enable(False)
-        if a.graph:
-            last["graph_ready"] = True
-        conv_ms = sum(e0.elapsed_time(e1) for _, _, _, e0, e1 in net.conv_timing)
-        conv_flops = sum(f for _, f, _, _, _ in net.conv_timing)
-        conv_direct_flops = sum(f for _, _, f, _, _ in net.conv_timing)
-        net.conv_timing = None
-        # (3) the same region R - 1 more times (same barrier + sync + MAX-over-ranks bracket, kernel timing off again): the
-        # spread of the number, measured where the number is. `value` stays the FIRST region.
         elapsed_all = [elapsed]
-        for _ in range(max(1, a.repeats) - 1):
-            elapsed_all.append(timed(a.steps)[0])
+        if a.full:
+            equal_serial = check_equal_serial(first_timed)
+            if sep_profile:
+                # per-kernel events cannot be recorded inside a graph replay, and with two streams a kernel's
+                # event pair also spans whatever the other stream ran in between: time the same kernels once
+                # more, eagerly on one stream
+                last["graph_ready"] = False
+                multi["on"] = False
+                net.conv_timing = []
+                _lib.profile_enable(True)
+                run(a.steps)
+                torch.cuda.synchronize()
+                multi["on"] = len(streams) > 1
+            kern = _lib.profile_report()
+            _lib.profile_enable(False)
+            if a.graph:
+                last["graph_ready"] = True
+            conv_ms = sum(e0.elapsed_time(e1) for _, _, _, e0, e1 in net.conv_timing)
+            conv_flops = sum(f for _, f, _, _, _ in net.conv_timing)
+            net.conv_timing = None
+            # (3) the same region R - 1 more times (same barrier + sync + MAX-over-ranks bracket, kernel timing off again): the
+            # spread of the number, measured where the number is. `value` stays the FIRST region.
+            for _ in range(max(1, a.repeats) - 1):
+                elapsed_all.append(timed(a.steps)[0])
         if a.latency:
             # per-frame latency: one batch at a time, upload -> kernels -> D2H -> host NMS, synchronously
             times = []
@@ -645,7 +707,7 @@ def main(argv=None):
                    "min_ms": times[0], "samples": len(times)}
 
     ag_us = None
-    if torch.distributed.is_initialized():   # every rank takes part (collective), before the other ranks leave
+    if torch.distributed.is_initialized() and a.full:   # every rank takes part (collective), before the other ranks leave
         try:
             ag_us = pdist.time_all_gather(last["det"].rows, last["det"].count)
         except Exception as e:
@@ -656,6 +718,44 @@ def main(argv=None):
     frames = B * world * a.steps
     ms_per_step = 1000.0 * elapsed / a.steps
     det = last["det"]
+    adl_rows = int((last["poses_weight"].sum(dim=1) > 0).sum().item()) if a.losses != "none" and last.get("poses_weight") is not None else 0
+    towers = 2 if a.input == "RGBD" else 1
+    name_of = "RGB-D" if a.input == "RGBD" else "RGB"
+    workload = ("%s: batch=%d/GPU %dx%d %s, %d classes; vgg16_convs (%d tower%s) + hough_voting(is_train=%d) + roi_pool + fc6-8"
+                % (cfg_name, B, W, H, name_of, C - 1, towers, "s" if towers > 1 else "", 1 if train else 0))
+    if a.losses != "none":
+        workload += " + hard_label + average_distance_loss (%d rows with pose targets)" % adl_rows
+    if G3 > 0:
+        workload += " + upscore deconv + backproject into a %d^3 grid (%.1f GB of voxel features per step)" % (G3, 4.0 * B * G3 ** 3 * (2 * 64 + C) / 1e9)
+    workload += " + all-gather + D2H + NMS; inputs from %s" % ("HBM (resident)" if a.resident_inputs else ("pinned host memory as raw uint8 / uint16 frames (H2D inside the timed region; the blobs are formed in the first kernel)" if a.raw_inputs else "pinned host memory (H2D inside the timed region)"))
+    out = {
+        "metric": "%s frames/sec (%dx%d, %d classes)" % (name_of, W, H, C - 1),
+        "value": frames / elapsed, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic (random frames; seeded VGG16 weights calibrated to O(1) activations — synth.init_calibrated, the "
+                                "weights the parity tests assert north_star's tolerance on; planted 1/8-res scene so the heads emit "
+                                "5 objects/frame with known poses — DESIGN.md §5)",
+        "config": {"workload": workload, "global_batch": B * world, "per_gpu_batch": B, "height": H, "width": W,
+                   "num_classes": C, "input_format": a.input, "losses": a.losses,
+                   "inputs": "resident" if a.resident_inputs else ("pinned-host-raw" if a.raw_inputs else "pinned-host"),
+                   "h2d_MB_per_step": None if a.resident_inputs else round(h2d_bytes / 1e6, 1),
+                   "parallelism": "dp%d (frames sharded, 1 all-gather of detections)" % world,
+                   "detections_per_step": ndet / a.steps, "adl_rows_with_targets": adl_rows},
+    }
+    if lat is not None:
+        out["latency"] = lat
+    out["process_group"] = ({"backend": torch.distributed.get_backend(), "ranks_seen": int(last.get("ranks_seen", 0)),
+                             "world_size": world, "collective": "all_gather_into_tensor of the packed detection block, once per step"}
+                            if torch.distributed.is_initialized() else
+                            {"backend": None, "ranks_seen": 1, "world_size": 1, "collective": "none (single process; --force-process-group runs it through RCCL)"})
+    out["per_rank"] = per_rank_fields(rank_elapsed, a.steps, 0 if a.resident_inputs else h2d_bytes)
+    out["process_group"]["shared_device"] = bool(a.shared_device)
+    out["process_group"]["host_numa"] = ({"node": numa[0], "cpus": numa[1]} if numa else None)
+    if not a.full:
+        out["value_note"] = ("value: the K timed steps after the W warm-up steps and %g s of untimed sustained-load pre-warm (GPU clocks "
+                             "ramp for seconds); --full adds value_cold, the spread over --repeats regions, the serial re-run check, "
+                             "per-kernel figures and rooflines, `secondary` and the CPU baseline" % a.prewarm_seconds)
+        return emit(out, pdist)
     lab = det.label_2d
     # Hough-vote roofline: algorithmic bytes per launch = B frames x (4*H*W + 12*N_fg + 56*R)
     # (SURVEY.md §8d A_hough), over the live HIP-event duration of the vote kernel.
@@ -723,11 +823,9 @@ def main(argv=None):
             # instruction) reads 0.5: a dependent stream holds the pipe ~4 cycles per instruction (profiles/r05_valu_rate_probe.txt).
             o["valu_active_share"] = 4.0 * ent["SQ_ACTIVE_INST_VALU"] / cyc
         return o
-    adl_rows = int((last["poses_weight"].sum(dim=1) > 0).sum().item()) if a.losses != "none" and last.get("poses_weight") is not None else 0
 
     # HBM-bound kernels of the library: algorithmic bytes per step / live event time per step
     act = lambda div, ch: 4.0 * B * (H // div) * (W // div) * ch
-    towers = 2 if a.input == "RGBD" else 1
     hbm = {
         "hard_label_fwd_kernel": 4.0 * B * H * W * (2 + C),
         "upscore_softmax_argmax": 4.0 * B * H * W * (C + 1) + act(8, C),     # (generic kernel or the compile-time-C instance)
@@ -775,27 +873,7 @@ def main(argv=None):
         + conv_ms / a.steps
     direct_flops_step = towers * 2.0 * B * (H * W) * 9 * (64 * 3 + 64 * 64 + (128 * 64 + 128 * 128) / 4 + (256 * 128 + 2 * 256 * 256) / 16
                                                          + (512 * 256 + 2 * 512 * 512) / 64 + 3 * 512 * 512 / 256)
-    name_of = "RGB-D" if a.input == "RGBD" else "RGB"
-    workload = ("%s: batch=%d/GPU %dx%d %s, %d classes; vgg16_convs (%d tower%s) + hough_voting(is_train=%d) + roi_pool + fc6-8"
-                % (cfg_name, B, W, H, name_of, C - 1, towers, "s" if towers > 1 else "", 1 if train else 0))
-    if a.losses != "none":
-        workload += " + hard_label + average_distance_loss (%d rows with pose targets)" % adl_rows
-    if G3 > 0:
-        workload += " + upscore deconv + backproject into a %d^3 grid (%.1f GB of voxel features per step)" % (G3, 4.0 * B * G3 ** 3 * (2 * 64 + C) / 1e9)
-    workload += " + all-gather + D2H + NMS; inputs from %s" % ("HBM (resident)" if a.resident_inputs else ("pinned host memory as raw uint8 / uint16 frames (H2D inside the timed region; the blobs are formed in the first kernel)" if a.raw_inputs else "pinned host memory (H2D inside the timed region)"))
-    out = {
-        "metric": "%s frames/sec (%dx%d, %d classes)" % (name_of, W, H, C - 1),
-        "value": frames / elapsed, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic (random frames; seeded VGG16 weights calibrated to O(1) activations — synth.init_calibrated, the "
-                                "weights the parity tests assert north_star's tolerance on; planted 1/8-res scene so the heads emit "
-                                "5 objects/frame with known poses — DESIGN.md §5)",
-        "config": {"workload": workload, "global_batch": B * world, "per_gpu_batch": B, "height": H, "width": W,
-                   "num_classes": C, "input_format": a.input, "losses": a.losses,
-                   "inputs": "resident" if a.resident_inputs else ("pinned-host-raw" if a.raw_inputs else "pinned-host"),
-                   "h2d_MB_per_step": None if a.resident_inputs else round(h2d_bytes / 1e6, 1),
-                   "parallelism": "dp%d (frames sharded, 1 all-gather of detections)" % world,
-                   "detections_per_step": ndet / a.steps, "adl_rows_with_targets": adl_rows},
+    out.update({
         **spread_fields(frames, elapsed_all, a.steps),
         "value_cold": frames / elapsed_cold,
         "value_note": "value: after %g s of untimed sustained-load pre-warm (GPU clocks ramp for seconds); value_cold: the same K "
@@ -837,16 +915,7 @@ def main(argv=None):
                            + ("; batches alternate over %d HIP streams (per-kernel times from a separate single-stream pass)" % len(streams) if len(streams) > 1 else ""),
         "kernels_us": {k: round(v["avg_us"], 2) for k, v in sorted(kern.items())},
         "kernel_calls_per_step": {k: round(v["calls"] / a.steps, 2) for k, v in sorted(kern.items())},
-    }
-    if lat is not None:
-        out["latency"] = lat
-    out["process_group"] = ({"backend": torch.distributed.get_backend(), "ranks_seen": int(last.get("ranks_seen", 0)),
-                             "world_size": world, "collective": "all_gather_into_tensor of the packed detection block, once per step"}
-                            if torch.distributed.is_initialized() else
-                            {"backend": None, "ranks_seen": 1, "world_size": 1, "collective": "none (single process; --force-process-group runs it through RCCL)"})
-    out["per_rank"] = per_rank_fields(rank_elapsed, a.steps, 0 if a.resident_inputs else h2d_bytes)
-    out["process_group"]["shared_device"] = bool(a.shared_device)
-    out["process_group"]["host_numa"] = ({"node": numa[0], "cpus": numa[1]} if numa else None)
+    })
     # the collective by itself: latency of one all-gather of the packed block, outside the timed region. A
     # single process has no communicator during the measurement; a 1-rank RCCL group is created here, after it, for this number only.
     try:
@@ -873,6 +942,10 @@ def main(argv=None):
             out["cpu_baseline"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         except Exception as e:  # the baseline is reported, never required for the GPU number
             out["cpu_baseline"] = {"error": repr(e)}
+    emit(out, pdist)
+
+
+def emit(out, pdist):
     # the JSON line is the LAST thing this process writes: tear the process group down first and flush the C
     # stdio buffer (RCCL prints a version banner through printf, which would otherwise land after the line)
     pdist.shutdown()

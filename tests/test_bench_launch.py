@@ -124,3 +124,26 @@ def test_step_pmc_file_belongs_to_this_build_of_the_kernels():
         assert ent["_src"] in pmc["_source_sha16"]
         assert ent["SQ_INSTS_VALU"] > 0 and ent["FETCH_SIZE_KB"] > 0 and ent["WRITE_SIZE_KB"] > 0, kernel
     assert pmc["wino43_mfma_kernel"]["SQ_VALU_MFMA_BUSY_CYCLES"] > 0 and pmc["wino43_mfma_kernel"]["SQ_INSTS_MFMA"] > 0
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: float32 files, small arrays whole, large ones cut to the same seeded sample in every run, 64 MB in all."""
+    import bench
+    import numpy as np
+    import torch
+    arrays = {"rois": np.arange(70, dtype=np.float32).reshape(10, 7),
+              "labels": (torch.arange(16 * 480 * 640, dtype=torch.int32) % 22).reshape(16, 480, 640),
+              "voxels": torch.arange(20_000_000, dtype=torch.float32), "more": torch.ones(12_000_000, dtype=torch.float64)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["labels.npy", "manifest.json", "more.npy", "rois.npy", "voxels.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64 << 20
+    man = json.load(open(str(tmp_path / "a" / "manifest.json")))
+    assert "sample" not in man["rois"] and man["voxels"]["shape"] == [20_000_000] and man["voxels"]["sample"]["of"] == 20_000_000
+    for f in files[:1] + files[2:]:
+        got, again = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert got.dtype == np.float32 and np.array_equal(got, again), f
+    assert np.array_equal(np.load(str(tmp_path / "a" / "rois.npy")), arrays["rois"])
+    v = np.load(str(tmp_path / "a" / "voxels.npy"))
+    assert v.size == man["voxels"]["sample"]["elements"] and np.all(np.diff(v) >= 0)   # sorted indices into an arange

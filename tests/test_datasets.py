@@ -1,6 +1,6 @@
 """CPU tests of posecnn_amd.datasets: the YCB-Video layout reader (lov.py:57-170) on a tree written
-here with PIL / scipy, the evaluation of lov.py:397-680 on hand-computable cases, and — when the
-reference tree is present (this container, not the GPU box) — the real fixtures: data/LOV/extents.txt
+here with PIL / scipy, the evaluation of lov.py:397-680 on hand-computable cases, and the reference's real
+fixtures (stored verbatim in tests/golden/: reference_data.npz, demo_images/): data/LOV/extents.txt
 and data/LINEMOD/extents.txt against the constants in posecnn_amd/config.py, the 21 model point clouds,
 the five demo frames."""
 import os
@@ -10,7 +10,7 @@ import pytest
 
 from posecnn_amd import config, datasets, pose_error
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 F = np.float32
 
 
@@ -109,34 +109,43 @@ def test_evaluate_result_add_and_adds(tmp_path):
     assert rep["frames"] == 1 and len(open(str(tmp_path / "out" / "segmentation.txt")).read().split()) == 22
 
 
-# ---- the reference's own fixtures (data, not code): only where the tree is mounted ---------------------
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "data", "LOV")), reason="reference tree absent (GPU box)")
+# ---- the reference's own fixtures (data, not code), stored under tests/golden ---------------------------
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    """The reference's data/ tree as far as the tests below read it: every text file byte for byte from
+    golden/reference_data.npz (one uint8 array of the file's bytes per relative path), the demo frames from golden/demo_images."""
+    root = str(tmp_path_factory.mktemp("reference"))
+    with np.load(os.path.join(GOLDEN, "reference_data.npz")) as z:
+        for rel in z.files:
+            os.makedirs(os.path.dirname(os.path.join(root, rel)), exist_ok=True)
+            with open(os.path.join(root, rel), "wb") as f:
+                f.write(z[rel].tobytes())
+    os.symlink(os.path.join(GOLDEN, "demo_images"), os.path.join(root, "data", "demo_images"))
+    return root
 
 
-@needs_ref
-def test_config_constants_equal_the_reference_files():
-    ext = datasets.load_object_extents(os.path.join(REF, "data", "LOV", "extents.txt"), 22)
+def test_config_constants_equal_the_reference_files(ref):
+    ext = datasets.load_object_extents(os.path.join(ref, "data", "LOV", "extents.txt"), 22)
     assert np.array_equal(ext, config.LOV_EXTENTS)                            # lov.py:161-170
-    lm = datasets.load_object_extents(os.path.join(REF, "data", "LINEMOD", "extents.txt"), 16)
+    lm = datasets.load_object_extents(os.path.join(ref, "data", "LINEMOD", "extents.txt"), 16)
     assert np.array_equal(lm, config.LINEMOD_EXTENTS_ALL) and np.array_equal(lm[:14], config.LINEMOD_EXTENTS)
-    classes = [l.strip() for l in open(os.path.join(REF, "data", "LOV", "classes.txt")) if l.strip()]
+    classes = [l.strip() for l in open(os.path.join(ref, "data", "LOV", "classes.txt")) if l.strip()]
     assert tuple(["__background__"] + classes) == config.LOV_CLASSES
     import json
-    cam = json.load(open(os.path.join(REF, "data", "LOV", "camera.json")))["rig"]["camera"][0]["camera_model"]["params"]
+    cam = json.load(open(os.path.join(ref, "data", "LOV", "camera.json")))["rig"]["camera"][0]["camera_model"]["params"]
     K = config.DEMO_INTRINSICS
     assert (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) == tuple(cam[:4])             # tools/demo.py:100
 
 
-@needs_ref
-def test_real_model_points_and_demo_frames():
-    pts, pts_all = datasets.load_object_points(os.path.join(REF, "data", "LOV", "models"), config.LOV_CLASSES)
+def test_real_model_points_and_demo_frames(ref):
+    pts, pts_all = datasets.load_object_points(os.path.join(ref, "data", "LOV", "models"), config.LOV_CLASSES)
     assert pts_all.shape == (22, config.NUM_MODEL_POINTS, 3) and min(p.shape[0] for p in pts[1:]) == 2620
     # every model fits its extent box (that is what extents.txt holds)
     for c in range(1, 22):
         span = pts[c].max(0) - pts[c].min(0)
         assert np.all(span <= config.LOV_EXTENTS[c] * 1.001 + 1e-4), config.LOV_CLASSES[c]
     for i in range(1, 6):
-        color = datasets.read_color_bgr(os.path.join(REF, "data", "demo_images", "%06d-color.png" % i))
-        depth = datasets.read_depth(os.path.join(REF, "data", "demo_images", "%06d-depth.png" % i))
+        color = datasets.read_color_bgr(os.path.join(ref, "data", "demo_images", "%06d-color.png" % i))
+        depth = datasets.read_depth(os.path.join(ref, "data", "demo_images", "%06d-depth.png" % i))
         assert color.shape == (480, 640, 3) and color.dtype == np.uint8
         assert depth.shape == (480, 640) and depth.dtype == np.uint16 and 0 < np.median(depth[depth > 0]) / config.DEMO_FACTOR_DEPTH < 3.0

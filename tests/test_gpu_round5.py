@@ -2,7 +2,7 @@
   * the mode the headline is measured in — THREE HIP streams, 16 RGB-D frames of 480x640, the fused first-layers
     kernel (138 KB of LDS, one workgroup per CU) co-resident with other batches' kernels — against the serial run,
     bit for bit, 24 batches (rows, fc7, poses_tanh, loss_pose);
-  * `bench.py` itself: `outputs_equal_serial` is true on a short default run;
+  * `bench.py` itself: `outputs_equal_serial` is true on a short --full run; a plain run times K steps and dumps its last one;
   * the multi-rank path rehearsed on one GPU: two ranks under the real launcher, both computing on cuda:0, gloo
     carrying the detection block (RCCL refuses duplicate devices) — real kernels, real shard offsets, `ranks_seen == 2`.
 """
@@ -105,7 +105,7 @@ def _json_line(stdout):
 def test_bench_reports_outputs_equal_serial(gpu):
     """`bench.py` (three streams) holds its own timed run to a serial re-run of the same batches and says so in the
     JSON line; a short run of the real configuration."""
-    r = subprocess.run([sys.executable, BENCH, "--steps", "6", "--warmup", "2", "--prewarm-seconds", "0", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--steps", "6", "--warmup", "2", "--prewarm-seconds", "0", "--no-cpu-baseline",
                         "--no-secondary"], env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = _json_line(r.stdout)
@@ -113,13 +113,37 @@ def test_bench_reports_outputs_equal_serial(gpu):
     d = out["outputs_equal_serial_detail"]
     assert d["batches_compared"] == 6 and d["mismatches"] == 0 and min(d["rows_per_batch"]) > 0
     assert "3 HIP streams" in out["step_submission"]
-    # round 6: the spread of the timed region and the per-rank block travel with every line (--repeats defaults to 5)
+    # round 6: the spread of the timed region and the per-rank block travel with every --full line (--repeats defaults to 5)
     assert out["repeats"] == 5 and len(out["value_all"]) == 5 and abs(out["value_all"][0] - out["value"]) < 0.01
     assert out["value_min"] <= out["value_median"] <= out["value_max"] and out["value_min"] > 0.8 * out["value_max"]
     pr = out["per_rank"]
     assert pr["ranks"] == 1 and abs(pr["ms_per_step_by_rank"][0] - out["ms_per_step"]) < 0.05 * out["ms_per_step"] and pr["h2d_GBps_per_rank"][0] > 1.0
     # the Hough counters are this build's (source-hash gate) and say what bounds the vote kernel: its vector ALUs
     assert out["roofline"]["traffic"] and 0.5 < out["roofline"]["valu_active_share"] < 1.3
+
+
+def test_plain_bench_run_is_the_headline_and_dumps_its_last_step(gpu, tmp_path):
+    """`bench.py` without --full: K timed steps and the headline fields, none of the --full measurements; --dump-outputs
+    writes the last timed step's outputs in float32, and a second process with the same arguments writes the same bits."""
+    dumped = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm-seconds", "0",
+                            "--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        out = _json_line(r.stdout)
+        assert out["steps"] == 3 and out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert "frames/sec" in out["metric"] and abs(out["value"] - 16 * 1000.0 / out["ms_per_step"]) < 1e-6 * out["value"]
+        assert not {"value_cold", "repeats", "outputs_equal_serial", "roofline", "kernels_us", "secondary", "cpu_baseline"} & set(out)
+        files = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d)) if f.endswith(".npy")}
+        assert set(files) == {"detections", "rois", "poses", "labels"}
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= 64 << 20
+        assert files["labels"].shape == (16, 480, 640) and files["labels"].max() > 0
+        assert files["rois"].shape[0] > 0 and files["rois"].shape == files["poses"].shape and files["detections"].shape[1] == 14
+        dumped.append(files)
+    for name in dumped[0]:
+        assert np.array_equal(dumped[0][name], dumped[1][name]), name
 
 
 def test_two_ranks_on_one_gpu_through_the_real_launcher(gpu):
@@ -129,7 +153,7 @@ def test_two_ranks_on_one_gpu_through_the_real_launcher(gpu):
     indices rank * B + i), barrier + MAX-over-ranks timing, one gather per step. Rank 0 must see both ranks' frames and
     twice one rank's detections. (the partitioning follows the reference's independent per-image loop,
     lib/hough_voting_gpu_layer/hough_voting_gpu_op.cc:369-377.)"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--shared-device", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--backend", "gloo", "--shared-device", "--steps", "4", "--warmup", "2",
                         "--prewarm-seconds", "0", "--no-cpu-baseline", "--no-secondary"],
                        env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
