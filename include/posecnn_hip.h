@@ -458,7 +458,10 @@ int pcnn_det_assemble_fwd(const float* rois, const float* poses_tanh, const floa
                           const int32_t* num_rows_dev, int rows, int row_stride, int num_classes, float* det_rows,
                           int32_t* det_count, void* stream);
 /* The same rows as the block one rank hands to the detection all-gather: det_block [ceil(rows / row_stride) + 1][14],
- * column 0 of the live rows shifted by `frame_offset` (global frame index = rank * B + local), last row = (count, 0, ...). */
+ * column 0 of the live rows shifted by `frame_offset` (global frame index = rank * B + local), last row = (count, 0, ...).
+ * "Live" is i s < *num_rows_dev, as for det_rows: when the count is no multiple of row_stride, the partial last group's row is
+ * written and shifted although det_count[0] = *num_rows_dev / s does not count it (dist.pack_detections leaves such a row
+ * unshifted; consumers read only the counted rows). */
 int pcnn_det_assemble_packed_fwd(const float* rois, const float* poses_tanh, const float* top_pose,
                                  const int32_t* num_rows_dev, int rows, int row_stride, int num_classes,
                                  float frame_offset, float* det_block, int32_t* det_count, void* stream);

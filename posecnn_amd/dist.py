@@ -141,7 +141,8 @@ def all_gather_packed(rows, count, frame_offset=0, group=None, packed=None):
     tensors only) the packed block is staged through the host: D2H on the batch's stream, wait for THAT copy,
     gather on gloo; the result is a host tensor, which `HostDrain` takes as it is."""
     # `packed`: the block already assembled on the device by ops.det_assemble(..., frame_offset=...) — same content as
-    # pack_detections(rows, count, frame_offset), without its four framework launches
+    # pack_detections(rows, count, frame_offset), without its four framework launches, on every row the count covers (a
+    # partial last group of a count that is no multiple of the row stride is written and shifted there, but not counted)
     buf = packed if packed is not None else pack_detections(rows, count, frame_offset)
     if not dist.is_initialized():
         return buf.unsqueeze(0)   # single process, no communicator: nothing to exchange

@@ -782,7 +782,9 @@ def det_assemble(rois, poses_tanh, top_pose, num_rows, row_stride=1, frame_offse
     translation, zeros past the device-side count; count [1] int32 = *num_rows // stride.
     With `frame_offset` (a rank's first global frame index) the same launch writes the block that rank hands to the
     detection all-gather — rows with column 0 shifted to global frame numbering + a last row (count, 0, ...) — and
-    returns (rows, count, block) with `rows` a view of the block's first rows."""
+    returns (rows, count, block) with `rows` a view of the block's first rows. Rows are written, and shifted in the block,
+    for every i * stride < *num_rows; when that count is no multiple of the stride, the partial last group's row is written
+    but not counted (count = *num_rows // stride)."""
     rois = _dev(rois, "rois", torch.float32)
     poses_tanh = _dev(poses_tanh, "poses_tanh", torch.float32)
     top_pose = _dev(top_pose, "top_pose", torch.float32)
