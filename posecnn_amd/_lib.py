@@ -1,4 +1,4 @@
-"""ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h).
+"""ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h and include/posecnn_hip_train.h).
 
 This is the Python-side analogue of the reference's ``tf.load_op_library('<op>.so')`` stubs
 (lib/hough_voting_gpu_layer/hough_voting_gpu_op.py:4-7 and siblings). The library is built
@@ -115,6 +115,14 @@ SIGNATURES = {
 }
 
 
+# the training-side entries of include/posecnn_hip_train.h (same library, same ABI version)
+TRAIN_SIGNATURES = {
+    "pcnn_vertex_targets_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "pcnn_smooth_l1_vertex_gt_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
+    "pcnn_smooth_l1_vertex_gt_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
+}
+
+
 def profile_enable(on=True):
     """Bracket every library kernel launch with HIP events on its launch stream."""
     check("pcnn_profile_enable", lib().pcnn_profile_enable(1 if on else 0))
@@ -159,7 +167,7 @@ def lib():
         # (round 6: `build()` followed by `smoke()` in one process did exactly that). So torch's goes in first, always.
         import torch  # noqa: F401
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args

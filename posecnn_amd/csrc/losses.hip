@@ -9,28 +9,9 @@
 // adds elements (blk*256 + t) + m*SL1_BLOCKS*256 for m ascending into f32 accumulators; a 256-leaf
 // halving tree in LDS, then a SL1_BLOCKS-leaf halving tree in a second one-block kernel. The CPU
 // checker restates exactly this order, so the loss matches bit for bit.
-#include "pcnn_device.h"
+#include "sl1_device.h"  // SL1_BLOCKS, sl1_elem, sl1_final_kernel: shared with vertex_targets.hip
 
 namespace {
-
-using namespace pcnn;
-
-constexpr int SL1_BLOCKS = 1024;
-
-__device__ __forceinline__ void sl1_elem(float p, float t, float w, float sigma2, float& in_loss,
-                                         float& dpred)
-{
-  const float diff = w * (p - t);
-  const float ad = fabsf(diff);
-  const float inv = div_rn(1.0f, sigma2);
-  if (ad < inv) {
-    in_loss = (diff * diff) * div_rn(sigma2, 2.0f);
-    dpred = w * (sigma2 * diff);
-  } else {
-    in_loss = ad - div_rn(0.5f, sigma2);
-    dpred = w * (diff > 0.f ? 1.0f : (diff < 0.f ? -1.0f : 0.0f));
-  }
-}
 
 __global__ __launch_bounds__(256) void sl1_partial_kernel(const float* __restrict__ pred,
                                                           const float* __restrict__ target,
@@ -61,31 +42,6 @@ __global__ __launch_bounds__(256) void sl1_partial_kernel(const float* __restric
   if (t == 0) {
     partial[blockIdx.x] = sl[0];
     partial[SL1_BLOCKS + blockIdx.x] = sw[0];
-  }
-}
-
-__global__ __launch_bounds__(SL1_BLOCKS / 2) void sl1_final_kernel(const float* __restrict__ partial,
-                                                                   float* __restrict__ out)
-{
-  __shared__ float sl[SL1_BLOCKS], sw[SL1_BLOCKS];
-  const int t = threadIdx.x;
-  sl[t] = partial[t];
-  sl[t + SL1_BLOCKS / 2] = partial[t + SL1_BLOCKS / 2];
-  sw[t] = partial[SL1_BLOCKS + t];
-  sw[t + SL1_BLOCKS / 2] = partial[SL1_BLOCKS + t + SL1_BLOCKS / 2];
-  __syncthreads();
-  for (int st = SL1_BLOCKS / 2; st >= 1; st >>= 1) {
-    if (t < st) {
-      sl[t] = sl[t] + sl[t + st];
-      sw[t] = sw[t] + sw[t + st];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const float denom = sw[0] + 1e-10f;
-    out[0] = div_rn(sl[0], denom);
-    out[1] = sl[0];
-    out[2] = sw[0];
   }
 }
 

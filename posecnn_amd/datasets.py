@@ -9,6 +9,10 @@ What the reference does in `lib/datasets/lov.py`, re-expressed for this framewor
     indexed by an image-set file (`keyframe.txt`, `val.txt`, ...; lov.py:57-135), read with PIL / scipy
     (the reference uses OpenCV): frames come back as the BGR uint8 / uint16 arrays `fcn._get_image_blob`
     expects, metadata as the dict `im_segment_single_frame` takes.
+  * `training_blobs`   the label half of a training minibatch (lib/gt_synthesize_layer/minibatch.py:270-525) from
+    `YCBVideo.frame()` dicts: label map, pose blob, meta data and — in place of the reference's vertex_targets /
+    vertex_weights tensors — the per-frame object table the device-side generator and the target-free vertex loss read
+    (`ops.vertex_targets`, `ops.smooth_l1_loss_vertex_gt`).
   * `Evaluator`   `evaluate_result` + `evaluate_segmentations` (lov.py:397-680): confusion histogram ->
     per-class IoU / accuracies, and per ground-truth object the ADD (ADD-S for the three symmetric
     classes) of every detection of its class against the 0.1 x |extents| threshold, accumulated into
@@ -17,12 +21,13 @@ What the reference does in `lib/datasets/lov.py`, re-expressed for this framewor
 
 Host-side numpy; nothing here touches the GPU.
 """
+import math
 import os
 
 import numpy as np
 
 from . import pose_error
-from .config import LOV_CLASSES
+from .config import LOV_CLASSES, make_meta_data
 
 # lov.py:465-468 / :605-608: the classes evaluated with ADD-S (adi)
 ADI_CLASSES = ("024_bowl", "036_wood_block", "061_foam_brick")
@@ -124,6 +129,114 @@ class YCBVideo(object):
         return {"index": self.image_index[i], "color": read_color_bgr(self.path(i, "color")),
                 "depth": read_depth(self.path(i, "depth")),
                 "label": read_label(self.path(i, "label")) if with_label else None, "meta": meta}
+
+
+MAX_VERTEX_OBJECTS = 64  # rows of a frame's object table (include/posecnn_hip_train.h)
+
+
+def mat2quat(R):
+    """Unit quaternion (w, x, y, z), w >= 0, of a (nearly) orthonormal 3x3 matrix: the eigenvector of the largest
+    eigenvalue of Bar-Itzhack's symmetric 4x4 matrix — what transforms3d.quaternions.mat2quat, which the reference
+    calls at minibatch.py:448, computes."""
+    R = np.asarray(R, dtype=np.float64)
+    (xx, xy, xz), (yx, yy, yz), (zx, zy, zz) = R
+    K = np.array([[xx - yy - zz, 0, 0, 0],
+                  [yx + xy, yy - xx - zz, 0, 0],
+                  [zx + xz, zy + yz, zz - xx - yy, 0],
+                  [zy - yz, xz - zx, yx - xy, xx + yy + zz]]) / 3.0
+    vals, vecs = np.linalg.eigh(K)   # reads the lower triangle
+    q = vecs[[3, 0, 1, 2], np.argmax(vals)]
+    return -q if q[0] < 0 else q
+
+
+def resize_nearest(im, scale):
+    """cv2.resize(im, None, None, fx=scale, fy=scale, interpolation=cv2.INTER_NEAREST) (minibatch.py:352): the output
+    has round(size * scale) rows / columns and pixel d reads source pixel min(floor(d / scale), size - 1)."""
+    if scale == 1.0:
+        return im
+    h, w = im.shape[:2]
+    ys = np.minimum(np.floor(np.arange(int(np.rint(h * scale))) * (1.0 / scale)).astype(np.int64), h - 1)
+    xs = np.minimum(np.floor(np.arange(int(np.rint(w * scale))) * (1.0 / scale)).astype(np.int64), w - 1)
+    return im[ys][:, xs]
+
+
+def training_blobs(frames, num_classes, im_scale=1.0, w_inside=10.0):
+    """The label blobs of one training minibatch from `YCBVideo.frame()` dicts (minibatch.py:300-525, the
+    SEGMENTATION / VERTEX_REG_2D branch without flipping). Returns a dict of numpy arrays:
+
+      gt_label_2d     int32 [B,H,W]   the label images padded to a multiple of 16 (`pad_im`), then scaled
+      vertex_objects  f32   [B,M,6]   rows (cls, mask_id, cx, cy, log_z, w) = (cls_indexes[j], 0, float32(im_scale *
+                                      center[j]), float32(log(poses[2,3,j])), w_inside), one per object of the frame's
+                                      -meta.mat, zero rows up to M = the largest count in the batch. This table and the
+                                      label map are everything `_generate_vertex_targets` (:543-602) reads:
+                                      `ops.vertex_targets` rebuilds its two [B,H,W,3C] outputs from them bit for bit
+                                      and `ops.smooth_l1_loss_vertex_gt` evaluates the loss without them.
+      vertex_instance int32 [B,H,W]   only if a frame takes the multi-instance path: its padded `mask` image (zeros for
+                                      the other frames)
+      poses           f32   [n,13]    (frame, cls, 0, 0, 0, 0, quaternion of R, T) per object (:439-450)
+      meta_data       f32   [B,1,1,48]  `config.make_meta_data(intrinsic_matrix, im_scale)` (:474-492)
+
+    w_inside is cfg.TRAIN.VERTEX_W_INSIDE (lib/fcn/config.py:64). Two-class training (num_classes == 2, :356-367): a
+    frame dict may carry 'cls_index' > 0 — the label becomes 1 on that class and 0 elsewhere and only that class's
+    objects are kept — and, when the class occurs more than once, 'mask' (the instance image, :429), whose value
+    k + 1 marks the pixels of the frame's k-th object: those rows get mask_id = k + 1."""
+    from .fcn import pad_im
+    if not frames:
+        raise ValueError("training_blobs: no frames")
+    labels, masks, tables, pose_rows, metas = [], [], [], [], []
+    for i, fr in enumerate(frames):
+        meta = fr["meta"]
+        im = resize_nearest(pad_im(np.asarray(fr["label"]), 16), im_scale).astype(np.int32)
+        cls_indexes = np.asarray(meta["cls_indexes"]).reshape(-1)
+        poses = np.asarray(meta["poses"], dtype=np.float64)
+        if poses.ndim == 2:
+            poses = poses.reshape(3, 4, 1)
+        center = np.asarray(meta["center"], dtype=np.float64).reshape(-1, 2)
+        mask_ids = np.zeros(len(cls_indexes))
+        mask = None
+        cls_index = int(fr.get("cls_index", 0))
+        if num_classes == 2 and cls_index > 0:
+            im = (im == cls_index).astype(np.int32)
+            ind = np.where(cls_indexes == cls_index)[0]
+            cls_indexes, poses, center = np.ones(len(ind)), poses[:, :, ind], center[ind]
+            mask_ids = np.zeros(len(ind))
+            if len(ind) > 1:
+                if fr.get("mask") is None:
+                    raise ValueError("training_blobs: frame %d has %d instances of class %d and no 'mask'" % (i, len(ind), cls_index))
+                mask = pad_im(np.asarray(fr["mask"]), 16).astype(np.int32)
+                if mask.shape != im.shape:
+                    raise ValueError("training_blobs: the instance mask of frame %d is not scaled with the label (im_scale != 1)" % i)
+                mask_ids = ind + 1.0
+        elif len(np.unique(cls_indexes)) < len(cls_indexes):
+            # the reference indexes an empty cls_indexes_old here (:436, :553)
+            raise ValueError("training_blobs: frame %d repeats a class; multi-instance frames need num_classes == 2 and 'cls_index'" % i)
+        n = len(cls_indexes)
+        if n > MAX_VERTEX_OBJECTS:
+            raise ValueError("training_blobs: frame %d has %d objects (at most %d)" % (i, n, MAX_VERTEX_OBJECTS))
+        tab = np.zeros((n, 6), dtype=np.float32)
+        qt = np.zeros((n, 13), dtype=np.float32)
+        for j in range(n):
+            c = (im_scale * center[j]).astype(np.float32)
+            tab[j] = (cls_indexes[j], mask_ids[j], c[0], c[1], np.float32(math.log(poses[2, 3, j])), w_inside)
+            qt[j, 0], qt[j, 1] = i, cls_indexes[j]
+            qt[j, 6:10] = mat2quat(poses[:, :3, j])
+            qt[j, 10:] = poses[:, 3, j]
+        labels.append(im)
+        masks.append(mask)
+        tables.append(tab)
+        pose_rows.append(qt)
+        metas.append(make_meta_data(meta["intrinsic_matrix"], im_scale))
+    if any(l.shape != labels[0].shape for l in labels):
+        raise ValueError("training_blobs: the frames of a batch must have one size")
+    M = max(t.shape[0] for t in tables)
+    objects = np.zeros((len(frames), M, 6), dtype=np.float32)
+    for i, t in enumerate(tables):
+        objects[i, :t.shape[0]] = t
+    out = {"gt_label_2d": np.stack(labels), "vertex_objects": objects, "poses": np.concatenate(pose_rows, axis=0),
+           "meta_data": np.stack(metas).reshape(len(frames), 1, 1, 48)}
+    if any(m is not None for m in masks):
+        out["vertex_instance"] = np.stack([np.zeros_like(labels[0]) if m is None else m for m in masks])
+    return out
 
 
 def fast_hist(gt, pred, n):

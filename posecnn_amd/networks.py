@@ -769,8 +769,9 @@ class vgg16_convs(Network):
 
     Constructor arguments follow vgg16_convs.py:5. `run(feed)` plays the role of
     `sess.run(net.enqueue_op, feed_dict)` + `sess.run([...])`: it binds the placeholders
-    (data, [data_p], gt_label_2d, keep_prob, vertex_targets/weights, poses, extents, meta_data,
-    points, symmetry) and evaluates the graph; outputs are read with `get_output(name)`.
+    (data, [data_p], gt_label_2d, keep_prob, vertex_targets/weights — or, in their place, the vertex_objects
+    [/ vertex_instance] of `datasets.training_blobs` —, poses, extents, meta_data, points, symmetry) and
+    evaluates the graph; outputs are read with `get_output(name)`.
     """
 
     def __init__(self, input_format, num_classes, num_units, scales, threshold_label, vote_threshold,

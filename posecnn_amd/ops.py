@@ -22,7 +22,7 @@ __all__ = [
     "conv1_1_conv1_2_fused_raw",
     "average_distance_loss", "backproject", "softmax_argmax", "deconv_bilinear", "bias_act_",
     "hough_voting_grad", "hard_label_grad", "hough_rows_capacity",
-    "upscore_softmax_argmax", "Workspace",
+    "upscore_softmax_argmax", "Workspace", "vertex_targets", "smooth_l1_loss_vertex_gt",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -923,6 +923,76 @@ def smooth_l1_loss_vertex(vertex_pred, vertex_targets, vertex_weights, sigma=1.0
     if pred.shape != target.shape or pred.shape != weight.shape:
         raise ValueError("vertex_pred, vertex_targets and vertex_weights must have the same shape")
     return _SmoothL1VertexFn.apply(pred, target, weight, float(sigma))[0]
+
+
+def _vertex_gt_args(gt_label_2d, objects, instance):
+    """(label int32 [B,H,W], objects f32 [B,M,6], instance int32 [B,H,W] | None) of include/posecnn_hip_train.h, checked."""
+    label = _dev(gt_label_2d, "gt_label_2d", torch.int32)
+    obj = _dev(objects, "objects", torch.float32)
+    if label.dim() != 3:
+        raise ValueError("gt_label_2d must be [B,H,W] (got %s)" % (tuple(label.shape),))
+    if obj.dim() != 3 or obj.shape[0] != label.shape[0] or obj.shape[2] != 6:
+        raise ValueError("objects must be [B,M,6] with B = %d (got %s)" % (label.shape[0], tuple(obj.shape)))
+    if instance is not None:
+        instance = _dev(instance, "instance", torch.int32)
+        if instance.shape != label.shape:
+            raise ValueError("instance must have the shape of gt_label_2d")
+    return label, obj, instance
+
+
+def vertex_targets(gt_label_2d, objects, num_classes, instance=None):
+    """lib/gt_synthesize_layer/minibatch.py:543-602 (`_generate_vertex_targets`, VERTEX_REG_2D) on the device:
+    gt_label_2d int32 [B,H,W], objects f32 [B,M,6] rows (cls, mask_id, cx, cy, log_z, w) as `datasets.training_blobs`
+    builds them, instance int32 [B,H,W] (multi-instance frames) -> (vertex_targets, vertex_weights) f32 [B,H,W,3C],
+    numpy's bits. Training itself does not need them: `smooth_l1_loss_vertex_gt` takes the same three inputs."""
+    label, obj, instance = _vertex_gt_args(gt_label_2d, objects, instance)
+    B, H, W = label.shape
+    C = int(num_classes)
+    targets = torch.empty((B, H, W, 3 * C), dtype=torch.float32, device=label.device)
+    weights = torch.empty((B, H, W, 3 * C), dtype=torch.float32, device=label.device)
+    check("pcnn_vertex_targets_fwd",
+          lib().pcnn_vertex_targets_fwd(_ptr(label), _ptr(instance), _ptr(obj), B, H, W, C, obj.shape[1], _ptr(targets),
+                                        _ptr(weights), _stream(label)))
+    return targets, weights
+
+
+class _SmoothL1VertexGtFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, label, instance, obj, sigma):
+        B, H, W, C3 = pred.shape
+        out = torch.empty(3, dtype=torch.float32, device=pred.device)
+        nbytes = c_size_t(0)
+        check("pcnn_smooth_l1_vertex_workspace_bytes", lib().pcnn_smooth_l1_vertex_workspace_bytes(ctypes.byref(nbytes)))
+        ws = _ws(pred.device, "smooth_l1").get(nbytes.value, pred.device)
+        check("pcnn_smooth_l1_vertex_gt_fwd",
+              lib().pcnn_smooth_l1_vertex_gt_fwd(_ptr(pred), _ptr(label), _ptr(instance), _ptr(obj), B, H, W, C3 // 3,
+                                                 obj.shape[1], float(sigma), _ptr(out), _ptr(ws), ws.numel(), _stream(pred)))
+        ctx.save_for_backward(pred, label, obj, out, instance)
+        ctx.sigma = float(sigma)
+        return out[0], out[1:].clone()
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_sums):
+        pred, label, obj, out, instance = ctx.saved_tensors
+        B, H, W, C3 = pred.shape
+        grad = torch.empty_like(pred)
+        up = grad_loss.reshape(1).to(torch.float32).contiguous()
+        check("pcnn_smooth_l1_vertex_gt_bwd",
+              lib().pcnn_smooth_l1_vertex_gt_bwd(_ptr(pred), _ptr(label), _ptr(instance), _ptr(obj), _ptr(out), _ptr(up),
+                                                 B, H, W, C3 // 3, obj.shape[1], ctx.sigma, _ptr(grad), _stream(pred)))
+        return grad, None, None, None, None
+
+
+def smooth_l1_loss_vertex_gt(vertex_pred, gt_label_2d, objects, instance=None, sigma=1.0):
+    """`smooth_l1_loss_vertex(vertex_pred, *vertex_targets(gt_label_2d, objects, C, instance), sigma)` — the same bits,
+    forward and backward — without the two [B,H,W,3C] tensors: both kernels read the label map and the object table.
+    vertex_pred must be finite where the weight is zero (include/posecnn_hip_train.h)."""
+    pred = _dev(vertex_pred, "vertex_pred", torch.float32)
+    label, obj, instance = _vertex_gt_args(gt_label_2d, objects, instance)
+    if pred.dim() != 4 or pred.shape[:3] != label.shape or pred.shape[3] % 3 != 0:
+        raise ValueError("vertex_pred must be [B,H,W,3C] over gt_label_2d %s (got %s)" % (tuple(label.shape), tuple(pred.shape)))
+    return _SmoothL1VertexGtFn.apply(pred, label, instance, obj, float(sigma))[0]
+
 
 
 def upscore_softmax_argmax(z, bias, kernel, stride, relu=True, want_score=False, want_prob=True, hard_gt=None,

@@ -37,6 +37,12 @@ def smooth_l1_loss_vertex(vertex_pred, vertex_targets, vertex_weights, sigma=1.0
     return ops.smooth_l1_loss_vertex(vertex_pred, vertex_targets, vertex_weights, sigma)
 
 
+def smooth_l1_loss_vertex_gt(vertex_pred, gt_label_2d, vertex_objects, vertex_instance=None, sigma=1.0):
+    """The same loss, same bits, from the label map and the object table of `datasets.training_blobs`: the
+    vertex_targets / vertex_weights tensors of minibatch.py:270-525 are never built."""
+    return ops.smooth_l1_loss_vertex_gt(vertex_pred, gt_label_2d, vertex_objects, vertex_instance, sigma)
+
+
 def loss_quaternion(pose_pred, pose_targets, pose_weights):
     """train.py:469-477 (the alternative pose loss the reference keeps around)."""
     distances = 1 - (pose_pred * pose_targets).sum(dim=1) ** 2
@@ -59,14 +65,22 @@ def regularization_loss(net, scale):
 
 def build_losses(net, cfg=TrainConfig):
     """The SINGLE_FRAME / VERTEX_REG_2D / POSE_REG branch of train_net (train.py:488-519), evaluated
-    on the layers of a finished `net.run(feed)`. Returns a dict of scalar tensors."""
+    on the layers of a finished `net.run(feed)`. Returns a dict of scalar tensors. A feed that carries `vertex_objects`
+    (and, for multi-instance frames, `vertex_instance`) instead of `vertex_targets` / `vertex_weights` takes the
+    target-free vertex loss."""
     out = {}
     out["loss_cls"] = loss_cross_entropy_single_frame(net.get_output("prob"), net.get_output("gt_label_weight"))
     out["loss_regu"] = regularization_loss(net, cfg.WEIGHT_REG)
     loss = out["loss_cls"] + out["loss_regu"]
     if net.vertex_reg:
-        out["loss_vertex"] = cfg.VERTEX_W * smooth_l1_loss_vertex(
-            net.get_output("vertex_pred"), net.get_output("vertex_targets"), net.get_output("vertex_weights"))
+        if "vertex_objects" in net.layers and "vertex_targets" not in net.layers:
+            # the feed of datasets.training_blobs: no [B,H,W,3C] targets, the loss reads label map + object table
+            instance = net.get_output("vertex_instance") if "vertex_instance" in net.layers else None
+            out["loss_vertex"] = cfg.VERTEX_W * smooth_l1_loss_vertex_gt(
+                net.get_output("vertex_pred"), net.get_output("gt_label_2d"), net.get_output("vertex_objects"), instance)
+        else:
+            out["loss_vertex"] = cfg.VERTEX_W * smooth_l1_loss_vertex(
+                net.get_output("vertex_pred"), net.get_output("vertex_targets"), net.get_output("vertex_weights"))
         loss = loss + out["loss_vertex"]
         if net.pose_reg and net.vertex_reg_2d:
             out["loss_pose"] = cfg.POSE_W * net.get_output("loss_pose")[0].reshape(())
