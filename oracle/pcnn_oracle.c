@@ -535,7 +535,7 @@ int oracle_roi_pool(const float* data, const float* rois, int B, int H, int W, i
   return 0;
 }
 
-/* ROIPoolBackward, roi_pooling_op_gpu.cu.cc:135-229 (gather form, ROIs ascending) */
+/* ROIPoolBackward, roi_pooling_op_gpu.cu.cc:135-229 (gather form, ROIs ascending), malformed ROIs as the forward pools them */
 int oracle_roi_pool_bwd(const float* top_diff, const float* rois, const int* argmax, int B, int H,
                         int W, int C, int R, int roi_cols, int PH, int PW, float scale,
                         int pool_channel, float* bottom_diff)
@@ -558,12 +558,17 @@ int oracle_roi_pool_bwd(const float* top_diff, const float* rois, const int* arg
       int roi_start_h = (int)roundf(roi[3] * scale);
       int roi_end_w = (int)roundf(roi[4] * scale);
       int roi_end_h = (int)roundf(roi[5] * scale);
-      if (!(w >= roi_start_w && w <= roi_end_w && h >= roi_start_h && h <= roi_end_h)) continue;
+      /* The forward forces a malformed ROI (end < start) to be one cell wide / high and pools that strip (:53-55).
+         The reference's backward repeats that clamp (:191-193) but only AFTER an in_roi test on the raw end (:174-175),
+         which no element passes when end < start: the strip's maxima never receive their gradient. Here the test uses
+         the clamped rectangle, so the backward is the derivative of the forward for every ROI; for well-formed ROIs
+         (end >= start) nothing changes, bit for bit. */
+      int roi_width = imax(roi_end_w - roi_start_w + 1, 1);
+      int roi_height = imax(roi_end_h - roi_start_h + 1, 1);
+      if (!(w >= roi_start_w && w <= roi_start_w + roi_width - 1 && h >= roi_start_h && h <= roi_start_h + roi_height - 1)) continue;
       size_t offset = pool_channel ? (size_t)roi_n * PH * PW : (size_t)roi_n * PH * PW * C;
       const float* otd = top_diff + offset;
       const int* oam = argmax + offset;
-      int roi_width = imax(roi_end_w - roi_start_w + 1, 1);
-      int roi_height = imax(roi_end_h - roi_start_h + 1, 1);
       float bin_size_h = (float)roi_height / (float)PH;
       float bin_size_w = (float)roi_width / (float)PW;
       int phstart = (int)floorf((float)(h - roi_start_h) / bin_size_h);

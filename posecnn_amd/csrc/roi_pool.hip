@@ -332,9 +332,12 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_binned(
         RoiEntry e;
         if (i < R) {
           const RoiGeom g = roi_geometry(rois + (size_t)i * roi_cols, scale, PH, PW);
-          // :161-166 — the element must lie inside the (unclipped) ROI rectangle
-          hit = g.batch == n && h >= g.sh && h <= g.eh && w_lo <= g.ew && w_hi - 1 >= g.sw;
-          e.idx = i; e.cls = g.cls; e.sw = g.sw; e.sh = g.sh; e.ew = g.ew; e.eh = g.eh;
+          // :174-175 — the element must lie inside the (unclipped) ROI rectangle. A malformed ROI (end < start) is
+          // forced to one cell by the forward (:53-55); the reference's backward tests the raw end first, so that
+          // cell never gets its gradient. The rectangle here is the one the forward pooled: end = max(end, start).
+          const int ew = max(g.ew, g.sw), eh = max(g.eh, g.sh);
+          hit = g.batch == n && h >= g.sh && h <= eh && w_lo <= ew && w_hi - 1 >= g.sw;
+          e.idx = i; e.cls = g.cls; e.sw = g.sw; e.sh = g.sh; e.ew = ew; e.eh = eh;
           e.bin_h = g.bin_h; e.bin_w = g.bin_w;
         }
         const unsigned long long mask = __ballot(hit);

@@ -111,7 +111,7 @@ def test_roi_pool_backward(gpu):
 def test_roi_pool_ties_wide_rois_and_long_roi_lists(gpu):
     """Cases aimed at the staged/binned kernels: heavy value ties (first maximum in (h, w) order must
     win), ROIs wider than the LDS column window (direct fallback), malformed ROIs (end < start: the
-    forward pools one cell, the backward's rectangle test drops it), a ROI table longer than the
+    forward pools one cell, and the backward returns that cell's gradient to it), a ROI table longer than the
     backward's LDS list (several compaction passes), C not a multiple of the chunk."""
     import torch
     from posecnn_amd import ops

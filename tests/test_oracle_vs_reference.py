@@ -129,6 +129,7 @@ def test_roi_pool_matches_reference_kernels(ref):
     rois[:, 2], rois[:, 3] = x1, y1
     rois[:, 4] = x1 + rng.uniform(-20, 200, R); rois[:, 5] = y1 + rng.uniform(-20, 200, R)
     rois[:5, 2:6] = np.round(rois[:5, 2:6] / 16) * 16 + 8
+    reached = 0
     for scale, pc in ((1 / 16.0, 0), (1 / 8.0, 0), (1.0, 0), (1 / 16.0, 1)):
         Cout = 1 if pc else C
         top = np.empty((R, 7, 7, Cout), F); arg = np.empty((R, 7, 7, Cout), np.int32)
@@ -138,7 +139,31 @@ def test_roi_pool_matches_reference_kernels(ref):
         g = rng.standard_normal(top.shape).astype(F)
         bd = np.empty((B, H, W, C), F)
         ref.ref_roi_pool_bwd(p(g), p(rois), p(arg), B, H, W, C, R, 7, 7, 7, c_float(scale), pc, p(bd))
-        bits_equal(bd, oracle.roi_pool_bwd(g, rois, arg, B, H, W, C, 7, 7, scale, pc), "bottom_diff")
+        # The one place where the oracle leaves the reference on purpose. A malformed ROI (end < start after rounding) is
+        # forced to one cell by the forward (:53-55) and pooled; the reference's backward repeats that clamp (:191-193) but
+        # behind an in_roi test on the raw end (:174-175) that no element passes, so those maxima never get their gradient.
+        # The oracle (and the kernel) return it: the backward is the derivative of the forward (tests/test_gpu_gradients.py).
+        # So: on the well-formed rows the oracle is the reference bit for bit, the reference ignores the malformed rows
+        # altogether, and the oracle's share for them is the scatter of their upstream gradient onto their argmax.
+        from np_ref import c_round
+        edge = np.array([[c_round(F(r[k]) * F(scale)) for k in (2, 3, 4, 5)] for r in rois])
+        malformed = (edge[:, 2] < edge[:, 0]) | (edge[:, 3] < edge[:, 1])
+        assert malformed.any() and not malformed.all()
+        g_well = g.copy(); g_well[malformed] = 0
+        bd_well = np.empty((B, H, W, C), F)
+        ref.ref_roi_pool_bwd(p(g_well), p(rois), p(arg), B, H, W, C, R, 7, 7, 7, c_float(scale), pc, p(bd_well))
+        bits_equal(bd, bd_well, "reference: malformed rows contribute nothing")
+        bits_equal(bd, oracle.roi_pool_bwd(g_well, rois, arg, B, H, W, C, 7, 7, scale, pc), "bottom_diff (well-formed rows)")
+        want = np.zeros((B, H * W * C), np.float64)
+        for n in np.flatnonzero(malformed):
+            hit = arg[n].ravel() >= 0
+            np.add.at(want[int(rois[n, 0])], arg[n].ravel()[hit], g[n].ravel()[hit].astype(np.float64))
+        got = oracle.roi_pool_bwd(g - g_well, rois, arg, B, H, W, C, 7, 7, scale, pc)
+        assert np.allclose(got.reshape(B, -1), want, rtol=0, atol=1e-5), "bottom_diff (malformed rows)"
+        reached += int(np.abs(want).sum() > 0)
+        full = oracle.roi_pool_bwd(g, rois, arg, B, H, W, C, 7, 7, scale, pc)
+        assert np.allclose(full, bd.astype(np.float64) + want.reshape(B, H, W, C), rtol=0, atol=1e-5)
+    assert reached >= 2       # malformed rows whose cell lies on the map, at more than one scale
 
 
 def test_hard_label_matches_reference_kernels(ref):

@@ -12,8 +12,10 @@ i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES" "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES SQ_WAIT_ANY" \
            "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o pmc -- python $R/bench.py --steps 3 --warmup 1 --prewarm-seconds 0 --streams 1 --no-cpu-baseline --no-secondary > $O/p$i.log 2>&1
-  python $R/tools/pmc_summary.py $O/p$i > $O/p$i.csv 2>> $O/p$i.log
+  # a pass that fails or hangs ends the collection: nothing more is started on a card that has just faulted
+  timeout -k 10 ${PASS_TIMEOUT:-300} rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o pmc -- python $R/bench.py --steps 3 --warmup 1 --prewarm-seconds 0 --streams 1 --no-cpu-baseline --no-secondary > $O/p$i.log 2>&1 \
+    || { echo "pass $i ($set) ended with status $?: see $O/p$i.log" >&2; tail -5 $O/p$i.log >&2; exit 1; }
+  python $R/tools/pmc_summary.py $O/p$i > $O/p$i.csv 2>> $O/p$i.log || { echo "pass $i: no summary" >&2; exit 1; }
   if [ -s $O/step_pmc.csv ]; then tail -n +2 $O/p$i.csv >> $O/step_pmc.csv; else cat $O/p$i.csv > $O/step_pmc.csv; fi
   rm -rf $O/p$i
 done
