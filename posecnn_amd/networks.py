@@ -187,8 +187,7 @@ class Network(object):
         # input channels.
         self.winograd_min_channels = 64
         self.winograd_tile = 4
-        self._wino_u = {}
-        self._fc_cache = {}    # transposed / zero-padded fc weights (not in the Winograd filter cache)
+        self._cache = {}       # slot -> tensors derived from variables (filter transforms, transposes, packings): `_derived`
         # F(4x4,3x3) layers with Cin, Cout multiples of 64: the 36 contractions + output transform run in
         # the library's own fp32-MFMA kernel (csrc/wino_mfma.hip); False = library batched GEMM + transform kernel
         self.winograd_mfma = True
@@ -246,6 +245,11 @@ class Network(object):
                 raw.out = self._bias_act(raw.y, raw.bias, raw.relu)
         return raw.out
 
+    def _conv12_fused_at(self, H, W):
+        """Does the one-kernel conv1_1 -> conv1_2 -> pool1 (csrc/conv_first.hip) apply to H x W frames? The core every site
+        shares; each adds its own conditions (the layer's channels, `defer_act`, the grouped trunk's preconditions)."""
+        return self.fused_conv12 and self.winograd_mfma and H % 16 == 0 and W % 16 == 0
+
     def _first_conv_v(self, pf):
         """V of conv1_2 with the pending conv1_1 `pf` evaluated inside its input transform (blobs or raw frames)."""
         x0 = pf.first[0]
@@ -257,13 +261,32 @@ class Network(object):
     def _winograd_filter(self, name, w, transposed=False):
         """U = G g G^T of a conv filter ([n*n, Cin, Cout]; transposed: [n*n, Cout, Cin] for the fused
         GEMM + output kernel), cached until the variable changes."""
-        key = (w.data_ptr(), w._version, self.winograd_tile, transposed)
-        hit = self._wino_u.get((name, transposed))
-        if hit is None or hit[0] != key:
+        def build():
             u = ops.winograd_filter(w, self.winograd_tile)
-            hit = (key, u.transpose(1, 2).contiguous() if transposed else u)
-            self._wino_u[(name, transposed)] = hit
-        return hit[1]
+            return u.transpose(1, 2).contiguous() if transposed else u
+        return self._derived(("wino", name, transposed), (w,), build, self.winograd_tile)
+
+    def _derived(self, slot, sources, build, extra=None):
+        """The value `build()` makes out of the variables `sources`, kept under `slot` until one of them changes — the ONE
+        place that decides whether a tensor derived from variables is still good. An entry holds its source tensors
+        themselves (so none of their addresses can be handed out again while it lives) and is valid iff every source is
+        still the same object at the same `_version` (in-place updates bump it; `load` installs new objects) and `extra`
+        (e.g. the Winograd tile) is equal. So a variable is changed by an in-place operation or by putting another tensor
+        into `vars` — never through `.data = ...`, which keeps both the object and its version. `load` drops the entries
+        of the variables it replaces; an entry of a slot that is no longer looked up otherwise lives as long as the network."""
+        hit = self._cache.get(slot)
+        if hit is not None and hit[2] == extra and len(hit[0]) == len(sources):
+            held, versions = hit[0], hit[1]
+            i = 0
+            for s in sources:   # (this runs for every layer of every step: an index walks faster than zip)
+                if s is not held[i] or s._version != versions[i]:
+                    break
+                i += 1
+            else:
+                return hit[3]
+        value = build()
+        self._cache[slot] = (tuple(sources), tuple(s._version for s in sources), extra, value)
+        return value
 
     def _winograd43_tail(self, name, v, w, b, relu, B_, H_, W_, c_i, c_o, timing):
         """Everything after the F(4x4,3x3) input transform: the library's fp32-MFMA kernel (contractions
@@ -305,14 +328,26 @@ class Network(object):
     def make_var(self, name, shape, initializer, trainable=False):
         """network.py:108-110. A variable asks for gradients when both the network and the layer are
         trainable (the reference passes `trainable` to tf.get_variable the same way)."""
-        if name not in self.vars:
-            self.vars[name] = initializer(shape).to(self.device)
-        v = self.vars[name]
+        v = self.vars.get(name)
+        if v is None:
+            v = self.vars[name] = initializer(shape).to(self.device)
         if self.trainable and trainable and not v.requires_grad and v.is_leaf:
             v.requires_grad_(True)
-        if tuple(v.shape) != tuple(shape):
+        if v.shape != tuple(shape):
             raise ValueError("variable %s has shape %s, layer wants %s" % (name, tuple(v.shape), tuple(shape)))
         return v
+
+    def _conv_vars(self, name, c_o, c_i, k_h, k_w, trainable, biased=True):
+        """The variables of a conv layer, weights before biases (network.py:169-185): filter [c_o, c_i, k_h, k_w] channels-last
+        (c_i: input channels per group; fan-in c_i k_h k_w) and zero biases (None when not `biased`)."""
+        w = self.make_var(name + "/weights", (c_o, c_i, k_h, k_w),
+                          lambda s: self._weight_init(c_i * k_h * k_w)(s).contiguous(memory_format=torch.channels_last), trainable)
+        return w, (self.make_var(name + "/biases", (c_o,), torch.zeros, trainable) if biased else None)
+
+    def _fc_vars(self, name, dim, num_out, trainable):
+        """The variables of an fc layer, weights [dim, num_out] before zero biases (network.py:409-411)."""
+        return (self.make_var(name + "/weights", (dim, num_out), self._weight_init(dim), trainable),
+                self.make_var(name + "/biases", (num_out,), torch.zeros, trainable))
 
     def _weight_init(self, fan_in):
         if self.init == "tf":  # tf.truncated_normal_initializer(0.0, stddev=0.001), network.py:170
@@ -355,6 +390,8 @@ class Network(object):
                         if pname == "weights" and t.dim() == 4 and op_name.startswith("upscore") and hasattr(self, "fused_heads"):
                             # a trained / non-bilinear deconv filter: conv1x1 and deconv no longer commute
                             self.fused_heads = False
+        live = set(map(id, self.vars.values()))   # what was derived from a variable that has left `vars` goes with it
+        self._cache = {slot: e for slot, e in self._cache.items() if live.issuperset(map(id, e[0]))}
 
     def load_file(self, path, ignore_missing=False):
         """Checkpoint ingestion. Accepts
@@ -403,10 +440,7 @@ class Network(object):
             c_i = 3 if raw_in else input.shape[-1]
         assert c_i % group == 0 and c_o % group == 0
         pending_first = input if isinstance(input, _RawConv) else None
-        w = self.make_var(name + "/weights", (c_o, c_i // group, k_h, k_w),
-                          lambda s: self._weight_init(c_i // group * k_h * k_w)(s).contiguous(memory_format=torch.channels_last),
-                          trainable)
-        b = self.make_var(name + "/biases", (c_o,), lambda s: torch.zeros(s), trainable) if biased else None
+        w, b = self._conv_vars(name, c_o, c_i // group, k_h, k_w, trainable, biased)
         assert s_h == 1 and s_w == 1 or padding == "VALID" or (k_h == 1 and k_w == 1), "strided SAME conv not on this path"
         pad = (k_h // 2, k_w // 2) if padding == "SAME" else 0
         if (self.fused_first_conv and b is not None and (k_h, k_w, c_i, group) == (3, 3, 3, 1) and padding == "SAME"
@@ -429,8 +463,8 @@ class Network(object):
                 if self.conv_timing is not None:
                     timing = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), 2.0 * B_ * H_ * W_ * c_i * 27)
                     timing[0].record()
-                if (self.fused_conv12 and self.winograd_mfma and name in self.defer_act and (c_i, c_o) == (64, 64)
-                        and pending_first.first[1].shape[3] == 64 and H_ % 16 == 0 and W_ % 16 == 0):
+                if (self._conv12_fused_at(H_, W_) and name in self.defer_act and (c_i, c_o) == (64, 64)
+                        and pending_first.first[1].shape[3] == 64):
                     # a 2x2 max_pool follows: conv1_1 -> conv1_2 -> pool1 as one LDS-resident kernel (csrc/conv_first.hip), launched
                     # by that max_pool; the library's own events time it
                     return _RawConv(None, b, relu, lazy12=(pending_first, name, w))
@@ -489,16 +523,15 @@ class Network(object):
                     return ops.winograd43_conv(v, ut, input.bias, B_, H_, W_, input.relu, pool=1)
                 if input.lazy12 is not None:
                     pf, name12, w2 = input.lazy12
-                    ut = self._winograd_filter(name12, w2, transposed=True)
-                    frag = self._wino_u.get((name12, "frag"))
-                    if frag is None or frag[0] is not ut:   # the filter bank in the order the kernel's lanes consume it
-                        frag = (ut, ops.conv12_fragment_major(ut))
-                        self._wino_u[(name12, "frag")] = frag
+                    # the filter bank in the order the kernel's lanes consume it
+                    frag = self._derived(("conv12_frag", name12), (w2,),
+                                         lambda: ops.conv12_fragment_major(self._winograd_filter(name12, w2, transposed=True)),
+                                         self.winograd_tile)   # (valid exactly as long as the U^T it is made of)
                     x0, w1 = pf.first
                     if _is_raw(x0):
                         return ops.conv1_1_conv1_2_fused_raw(x0 if x0.dtype == torch.uint8 else None, x0 if x0.dtype == torch.uint16 else None,
-                                                             w1, pf.bias, frag[1], input.bias, pf.relu, input.relu, ut2_layout=1)
-                    return ops.conv1_1_conv1_2_fused(x0, w1, pf.bias, frag[1], input.bias, pf.relu, input.relu, groups=1, ut2_layout=1)
+                                                             w1, pf.bias, frag, input.bias, pf.relu, input.relu, ut2_layout=1)
+                    return ops.conv1_1_conv1_2_fused(x0, w1, pf.bias, frag, input.bias, pf.relu, input.relu, groups=1, ut2_layout=1)
                 if input.wino is not None and input.dual and self.winograd_tile == 4:
                     m, B_, H_, W_ = input.wino
                     input.out, pooled = ops.winograd43_output_both(m, input.bias, B_, H_, W_, input.relu)
@@ -579,9 +612,8 @@ class Network(object):
         else:
             dim = int(input.shape[-1]) if num_in == -1 else int(num_in)
             feed_in = input
-        w = self.make_var(name + "/weights", (dim, num_out), self._weight_init(dim), trainable)
-        b = self.make_var(name + "/biases", (num_out,), lambda s: torch.zeros(s), trainable)
-        rows = getattr(self, "rows_count", None)
+        w, b = self._fc_vars(name, dim, num_out, trainable)
+        rows = self.rows_count
         route = self._fc_route(feed_in.is_cuda, feed_in.shape[0] if feed_in.dim() == 2 else None, dim, num_out,
                                self._fc_wants_grad(w, layer_trainable=trainable, feed_requires_grad=feed_in.requires_grad), rows is not None)
         if route == "skinny":
@@ -599,16 +631,18 @@ class Network(object):
         will = (w is not None and w.requires_grad) or (self.trainable and layer_trainable and (w is None or w.is_leaf))
         return torch.is_grad_enabled() and (will or feed_requires_grad)
 
-    def _fc_route(self, is_cuda, n_rows, dim, num_out, wants_grad, has_count):
-        """Which implementation `fc` takes — ONE predicate for `fc` itself and for `fc_masks_dead_rows` (the two used
-        to restate it separately): "skinny" (csrc/fc_skinny.hip: a device-counted buffer of at most SKINNY_MAX_ROWS rows),
+    def _fc_route(self, is_cuda, n_rows, dim, num_out, wants_grad, has_count, padded_width=False):
+        """Which implementation `fc` takes — ONE predicate for `fc` itself, for `fc_tanh` and for `fc_masks_dead_rows` (ADVICE r5:
+        they used to restate it separately): "skinny" (csrc/fc_skinny.hip: a device-counted buffer of at most SKINNY_MAX_ROWS rows),
         "rows" (csrc/fc_mfma.hip: any device-counted buffer whose shapes the kernel takes) or "addmm" (the framework: every
-        trainable graph under autograd, CPU tensors, odd shapes). The two library routes never read a row at or past the count."""
+        trainable graph under autograd, CPU tensors, odd shapes). The two library routes never read a row at or past the count.
+        `n_rows` is None for an input that is not 2-D. `padded_width`: the caller zero-pads the filter to the row kernel's 64
+        columns itself (`fc_tanh`), so that route only needs the float4 stores' num_out % 4 == 0."""
         if not is_cuda or wants_grad or not has_count:
             return "addmm"
         if self.fc_skinny and n_rows is not None and 1 <= n_rows <= ops.SKINNY_MAX_ROWS and dim % 16 == 0:
             return "skinny"
-        if dim % 64 == 0 and dim >= 128 and num_out % 64 == 0:
+        if dim % 64 == 0 and dim >= 128 and num_out % (4 if padded_width else 64) == 0:
             return "rows"
         return "addmm"
 
@@ -623,17 +657,7 @@ class Network(object):
 
     def _fc_wt(self, name, w):
         """The TF weight variable [in, out] transposed to [out, in] (K contiguous rows for the kernels), cached."""
-        key = (w.data_ptr(), w._version)
-        hit = self._fc_cache.get(("fc", name))
-        if hit is None or hit[0] != key:
-            hit = (key, w.detach().t().contiguous())
-            self._fc_cache[("fc", name)] = hit
-        return hit[1]
-
-    def _fc_skinny_ok(self, feed_in, dim, w):
-        return (self.fc_skinny and getattr(self, "rows_count", None) is not None and feed_in.is_cuda and feed_in.dim() == 2
-                and 1 <= feed_in.shape[0] <= ops.SKINNY_MAX_ROWS and dim % 16 == 0
-                and not (torch.is_grad_enabled() and (w.requires_grad or feed_in.requires_grad)))
+        return self._derived(("fc_wt", name), (w,), lambda: w.detach().t().contiguous())
 
     def fc_tanh(self, num_out, name, tanh_name, num_in=-1):
         """`.fc(num_out, relu=False, name=name).tanh(name=tanh_name)` (fc8 -> poses_tanh, vgg16_convs.py:192-193);
@@ -642,29 +666,28 @@ class Network(object):
         if isinstance(x, tuple):
             x = x[0]
         dim = int(x.shape[-1]) if num_in == -1 else int(num_in)
-        w = self.make_var(name + "/weights", (dim, num_out), self._weight_init(dim), True)
-        b = self.make_var(name + "/biases", (num_out,), lambda s: torch.zeros(s), True)
-        if x.dim() == 2 and self._fc_skinny_ok(x, dim, w):
-            y, t = ops.fc_skinny(x.contiguous(), self._fc_wt(name, w), b, "tanh", num_rows=self.rows_count)
-            self.layers[name], self.layers[tanh_name] = y, t
-            return self.feed(t)
-        if (x.dim() == 2 and getattr(self, "rows_count", None) is not None and x.is_cuda and dim % 64 == 0 and dim >= 128
-                and num_out % 4 == 0 and not (torch.is_grad_enabled() and (w.requires_grad or x.requires_grad))):
+        w, b = self._fc_vars(name, dim, num_out, True)
+        rows = self.rows_count
+        route = "addmm" if x.dim() != 2 else self._fc_route(
+            x.is_cuda, x.shape[0], dim, num_out, self._fc_wants_grad(w, feed_requires_grad=x.requires_grad), rows is not None,
+            padded_width=True)
+        if route == "addmm":
+            return self.fc(num_out, relu=False, name=name, num_in=num_in).tanh(name=tanh_name)
+        if route == "skinny":
+            y, t = ops.fc_skinny(x.contiguous(), self._fc_wt(name, w), b, "tanh", num_rows=rows)
+        else:
             # more rows than the skinny kernel takes (a batch): the row kernel on a zero-padded filter, tanh in its epilogue
-            key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
-            hit = self._fc_cache.get(("fc_pad", name))
-            if hit is None or hit[0] != key:
+            def build():
                 npad = (num_out + 63) // 64 * 64
                 wp = torch.zeros((npad, dim), dtype=torch.float32, device=w.device)
                 wp[:num_out] = w.detach().t()
                 bp = torch.zeros((npad,), dtype=torch.float32, device=w.device)
                 bp[:num_out] = b.detach()
-                hit = (key, wp, bp)
-                self._fc_cache[("fc_pad", name)] = hit
-            y, t = ops.fc_rows_cols(x.contiguous(), hit[1], hit[2], num_out, "tanh", num_rows=self.rows_count)
-            self.layers[name], self.layers[tanh_name] = y, t
-            return self.feed(t)
-        return self.fc(num_out, relu=False, name=name, num_in=num_in).tanh(name=tanh_name)
+                return wp, bp
+            wp, bp = self._derived(("fc_pad", name), (w, b), build)
+            y, t = ops.fc_rows_cols(x.contiguous(), wp, bp, num_out, "tanh", num_rows=rows)
+        self.layers[name], self.layers[tanh_name] = y, t
+        return self.feed(t)
 
     # ---- element-wise -----------------------------------------------------------------------------
     @layer
@@ -826,7 +849,6 @@ class vgg16_convs(Network):
         self.fuse_hard_label = False  # fcn.im_segment_batch(with_losses=True) on a graph built without the loss layers: gt_label_weight from the label head's launch
         self.mfma_heads = True        # big batches: add_score / add_score_vertex + the 1/8-resolution `score` / `vertex_pred` products in one launch per head
         self.head_gemm = True         # 1x1 head convs (incl. the RGB-D concat) on the library's own fp32-MFMA row kernel
-        self._head_wt = {}
 
     def run(self, feed, planted=None):
         self.layers = dict(feed)
@@ -840,9 +862,7 @@ class vgg16_convs(Network):
     def _conv1x1_lowres(self, x, name, c_o, c_i):
         """The 1x1 conv `name` (same variables as Network.conv would create) applied WITHOUT bias
         or ReLU; returns (z, bias) for the fused deconv epilogue."""
-        w = self.make_var(name + "/weights", (c_o, c_i, 1, 1),
-                          lambda s: self._weight_init(c_i)(s).contiguous(memory_format=torch.channels_last))
-        b = self.make_var(name + "/biases", (c_o,), lambda s: torch.zeros(s))
+        w, b = self._conv_vars(name, c_o, c_i, 1, 1, False)
         return _nhwc(F.conv2d(_nchw(x), w, None)), b
 
     def _head_conv1x1(self, sources, c_o, name, relu=True):
@@ -863,20 +883,15 @@ class vgg16_convs(Network):
             else:
                 self.feed(sources[0])
             return self.conv(1, 1, c_o, 1, 1, name=name, relu=relu, c_i=c_i)
-        w = self.make_var(name + "/weights", (c_o, c_i, 1, 1),
-                          lambda s: self._weight_init(c_i)(s).contiguous(memory_format=torch.channels_last), self.trainable)
-        b = self.make_var(name + "/biases", (c_o,), lambda s: torch.zeros(s), self.trainable)
-        key = (w.data_ptr(), w._version)
-        hit = self._head_wt.get(name)
-        if hit is None or hit[0] != key:
+        w, b = self._conv_vars(name, c_o, c_i, 1, 1, self.trainable)
+        def build():
             w2 = w.detach().reshape(c_o, c_i)
             parts, off = [], 0
             for c in cis:
                 parts.append(w2[:, off:off + c].contiguous())
                 off += c
-            hit = (key, parts, torch.zeros_like(b))
-            self._head_wt[name] = hit
-        parts, zero_b = hit[1], hit[2]
+            return parts, torch.zeros_like(b)
+        parts, zero_b = self._derived(("head", name), (w,), build, tuple(cis))
         B_, h, w_ = xs[0].shape[:3]
         partial = None
         for j in range(len(xs) - 1, 0, -1):     # the other towers first, as addends
@@ -903,14 +918,7 @@ class vgg16_convs(Network):
 
     def _trunk_vars(self, suffix):
         """Creates (on first use) the variables of one tower in the order Network.conv would."""
-        t = self.trainable
-        out = []
-        for name, ci, co, _ in self.TRUNK:
-            w = self.make_var(name + suffix + "/weights", (co, ci, 3, 3),
-                              lambda s_, ci=ci: self._weight_init(ci * 9)(s_).contiguous(memory_format=torch.channels_last), t)
-            b = self.make_var(name + suffix + "/biases", (co,), lambda s_: torch.zeros(s_), t)
-            out.append((w, b))
-        return out
+        return [self._conv_vars(name + suffix, co, ci, 3, 3, self.trainable) for name, ci, co, _ in self.TRUNK]
 
     def _can_group_towers(self):
         d = self.layers.get('data')
@@ -943,9 +951,7 @@ class vgg16_convs(Network):
             B2, H, W, _ = x.shape
             B = B2 // 2
         va, vb = self._trunk_vars(""), self._trunk_vars("_p")
-        key = tuple((w.data_ptr(), w._version, b.data_ptr(), b._version) for w, b in va + vb)
-        hit = self._wino_u.get("grouped")
-        if hit is None or hit[0] != key:
+        def build():
             packed = []
             for (name, ci, co, _), (w0, b0), (w1, b1) in zip(self.TRUNK, va, vb):
                 bias = torch.stack([b0, b1]).contiguous()
@@ -954,23 +960,20 @@ class vgg16_convs(Network):
                 else:
                     wt = torch.stack([ops.winograd_filter(w0, 4).transpose(1, 2), ops.winograd_filter(w1, 4).transpose(1, 2)]).contiguous()
                 packed.append((wt, bias))
-            hit = (key, packed)
-            self._wino_u["grouped"] = hit
-        packed = hit[1]
+            return packed
+        packed = self._derived("grouped", [t for wb in va + vb for t in wb], build)
         y, h, w_ = None, H, W
         for li, (name, ci, co, pool) in enumerate(self.TRUNK):
             wt, bias = packed[li]
             if ci == 3:
                 continue   # conv1_1 is evaluated inside conv1_2's input transform
-            if li == 1 and self.fused_conv12 and pool == "pool1" and co == 64 and H % 16 == 0 and W % 16 == 0:
+            if li == 1 and self._conv12_fused_at(H, W) and pool == "pool1" and co == 64:
                 # conv1_1 -> conv1_2 -> pool1 in one kernel: V (2.25 x 78.6 MB per frame) never touches HBM (csrc/conv_first.hip)
-                frag = self._wino_u.get("conv12_frag")
-                if frag is None or frag[0] is not wt:
-                    # the filter bank fragment-major (one contiguous KB per B-operand load)
-                    frag = (wt, ops.conv12_fragment_major(wt), 1)
-                    self._wino_u["conv12_frag"] = frag
-                y = (ops.conv1_1_conv1_2_fused_raw(d, dp, packed[0][0], packed[0][1], frag[1], bias, ut2_layout=frag[2]) if raw
-                     else ops.conv1_1_conv1_2_fused(x, packed[0][0], packed[0][1], frag[1], bias, groups=2, ut2_layout=frag[2]))
+                # the filter bank fragment-major (one contiguous KB per B-operand load). Keyed on the two conv1_2 filters it is
+                # made of: it used to be rebuilt with the whole packing, i.e. also when any other trunk variable changed
+                frag = self._derived(("conv12_frag", "grouped"), (va[li][0], vb[li][0]), lambda: ops.conv12_fragment_major(wt))
+                y = (ops.conv1_1_conv1_2_fused_raw(d, dp, packed[0][0], packed[0][1], frag, bias, ut2_layout=1) if raw
+                     else ops.conv1_1_conv1_2_fused(x, packed[0][0], packed[0][1], frag, bias, groups=2, ut2_layout=1))
                 h, w_ = h // 2, w_ // 2
                 continue
             if li == 1:
@@ -1000,7 +1003,7 @@ class vgg16_convs(Network):
         towers = 2 if self.input_format == 'RGBD' else 1
         act = lambda div, ch: 4.0 * B * (H // div) * (W // div) * ch
         x_in = (act(2, 64) + act(2, 128) + act(4, 128) + 2 * act(4, 256) + act(8, 256) + 2 * act(8, 512) + 3 * act(16, 512))
-        fused = self.fused_conv12 and self.winograd_mfma and H % 16 == 0 and W % 16 == 0   # (the first two layers as one kernel)
+        fused = self._conv12_fused_at(H, W)   # (the first two layers as one kernel)
         t = {"wino43_input_kernel": towers * 3.25 * x_in}                             # reads X, writes V = 2.25 X
         if not fused:
             t["conv3x3_c3_wino43_kernel"] = towers * (act(1, 3) + 2.25 * act(1, 64))      # reads the frame, writes V of conv1_2
@@ -1011,7 +1014,7 @@ class vgg16_convs(Network):
         towers = 2 if self.input_format == 'RGBD' else 1
         tiles = lambda div: B * ((H // div + 3) // 4) * ((W // div + 3) // 4)
         div = {"1": 1, "2": 2, "3": 4, "4": 8, "5": 16}
-        fused = self.fused_conv12 and self.winograd_mfma and H % 16 == 0 and W % 16 == 0
+        fused = self._conv12_fused_at(H, W)
         fl = sum(2.0 * 36 * tiles(div[n[4]]) * ci * co for n, ci, co, _ in self.TRUNK if ci != 3 and not (fused and n == "conv1_2"))
         t = {"wino43_mfma_kernel": towers * fl}
         if fused:   # conv1_1 + conv1_2 + pool1 in one kernel: its matrix work is conv1_2's Winograd-domain contraction
@@ -1049,52 +1052,25 @@ class vgg16_convs(Network):
                 self.layers[k + sfx] = torch.cat(v, dim=0).contiguous()
         return self
 
-    def setup(self):
+    def _tower(self, src, sfx):
+        """One VGG16 tower (vgg16_convs.py:36-52; :53-67 with '_p') on the layer DSL, off the TRUNK table."""
+        self.feed(src)
         t = self.trainable
+        for name, ci, co, pool in self.TRUNK:
+            self.conv(3, 3, co, 1, 1, name=name + sfx, c_i=ci, trainable=t)
+            if pool is not None:
+                self.max_pool(2, 2, 2, 2, name=pool + sfx)
+
+    def setup(self):
         if self.reference_trunk is not None:
             self._trunk_reference(self.reference_trunk)
             return self._setup_heads()
         if self._can_group_towers():
             self._trunk_grouped()
             return self._setup_heads()
-        (self.feed('data')
-             .conv(3, 3, 64, 1, 1, name='conv1_1', c_i=3, trainable=t)
-             .conv(3, 3, 64, 1, 1, name='conv1_2', c_i=64, trainable=t)
-             .max_pool(2, 2, 2, 2, name='pool1')
-             .conv(3, 3, 128, 1, 1, name='conv2_1', c_i=64, trainable=t)
-             .conv(3, 3, 128, 1, 1, name='conv2_2', c_i=128, trainable=t)
-             .max_pool(2, 2, 2, 2, name='pool2')
-             .conv(3, 3, 256, 1, 1, name='conv3_1', c_i=128, trainable=t)
-             .conv(3, 3, 256, 1, 1, name='conv3_2', c_i=256, trainable=t)
-             .conv(3, 3, 256, 1, 1, name='conv3_3', c_i=256, trainable=t)
-             .max_pool(2, 2, 2, 2, name='pool3')
-             .conv(3, 3, 512, 1, 1, name='conv4_1', c_i=256, trainable=t)
-             .conv(3, 3, 512, 1, 1, name='conv4_2', c_i=512, trainable=t)
-             .conv(3, 3, 512, 1, 1, name='conv4_3', c_i=512, trainable=t)
-             .max_pool(2, 2, 2, 2, name='pool4')
-             .conv(3, 3, 512, 1, 1, name='conv5_1', c_i=512, trainable=t)
-             .conv(3, 3, 512, 1, 1, name='conv5_2', c_i=512, trainable=t)
-             .conv(3, 3, 512, 1, 1, name='conv5_3', c_i=512, trainable=t))
-
+        self._tower('data', '')
         if self.input_format == 'RGBD':
-            (self.feed('data_p')
-                 .conv(3, 3, 64, 1, 1, name='conv1_1_p', c_i=3, trainable=t)
-                 .conv(3, 3, 64, 1, 1, name='conv1_2_p', c_i=64, trainable=t)
-                 .max_pool(2, 2, 2, 2, name='pool1_p')
-                 .conv(3, 3, 128, 1, 1, name='conv2_1_p', c_i=64, trainable=t)
-                 .conv(3, 3, 128, 1, 1, name='conv2_2_p', c_i=128, trainable=t)
-                 .max_pool(2, 2, 2, 2, name='pool2_p')
-                 .conv(3, 3, 256, 1, 1, name='conv3_1_p', c_i=128, trainable=t)
-                 .conv(3, 3, 256, 1, 1, name='conv3_2_p', c_i=256, trainable=t)
-                 .conv(3, 3, 256, 1, 1, name='conv3_3_p', c_i=256, trainable=t)
-                 .max_pool(2, 2, 2, 2, name='pool3_p')
-                 .conv(3, 3, 512, 1, 1, name='conv4_1_p', c_i=256, trainable=t)
-                 .conv(3, 3, 512, 1, 1, name='conv4_2_p', c_i=512, trainable=t)
-                 .conv(3, 3, 512, 1, 1, name='conv4_3_p', c_i=512, trainable=t)
-                 .max_pool(2, 2, 2, 2, name='pool4_p')
-                 .conv(3, 3, 512, 1, 1, name='conv5_1_p', c_i=512, trainable=t)
-                 .conv(3, 3, 512, 1, 1, name='conv5_2_p', c_i=512, trainable=t)
-                 .conv(3, 3, 512, 1, 1, name='conv5_3_p', c_i=512, trainable=t))
+            self._tower('data_p', '_p')
         return self._setup_heads()
 
     def _mfma_head_ok(self, c_i, c_o):
@@ -1120,23 +1096,15 @@ class vgg16_convs(Network):
                 and (up_name + "/weights") not in self.vars
                 and not (torch.is_grad_enabled() and self.trainable)):
             return None
-        w = self.make_var(conv_name + "/weights", (c_o, c_i, 1, 1),
-                          lambda s: self._weight_init(c_i)(s).contiguous(memory_format=torch.channels_last))
-        b = self.make_var(conv_name + "/biases", (c_o,), lambda s: torch.zeros(s))
-        key = (w.data_ptr(), w._version)
-        hit = self._head_wt.get(("lowres", conv_name))
-        if hit is None or hit[0] != key:
-            hit = (key, w.detach().reshape(c_o, c_i).t().contiguous())     # [units, out]: the TF variable [1,1,in,out] as it is
-            self._head_wt[("lowres", conv_name)] = hit
+        w, b = self._conv_vars(conv_name, c_o, c_i, 1, 1, False)
         planted = self.planted.get(plant_key) if self.planted is not None else None
-        if not self._mfma_head_ok(c_i, c_o):
-            add, z = ops.head_lowres(a, b5, hit[1], planted=planted, kernel=4, stride=2)
+        if not self._mfma_head_ok(c_i, c_o):   # the filter [units, out]: the TF variable [1,1,in,out] as it is
+            w_t = self._derived(("lowres", conv_name), (w,), lambda: w.detach().reshape(c_o, c_i).t().contiguous())
+            add, z = ops.head_lowres(a, b5, w_t, planted=planted, kernel=4, stride=2)
         else:
-            hitm = self._head_wt.get(("lowres_mfma", conv_name))
-            if hitm is None or hitm[0] != key:
-                hitm = (key, ops.head_lowres_mfma_filter(hit[1]))
-                self._head_wt[("lowres_mfma", conv_name)] = hitm
-            add, z = ops.head_lowres_mfma(a, b5, hitm[1], c_o, planted=planted, kernel=4, stride=2)
+            w_nk = self._derived(("lowres_mfma", conv_name), (w,),
+                                 lambda: ops.head_lowres_mfma_filter(w.detach().reshape(c_o, c_i).t()))
+            add, z = ops.head_lowres_mfma(a, b5, w_nk, c_o, planted=planted, kernel=4, stride=2)
         self.layers[up_name] = _Lazy(lambda: self._deconv_bilinear(b5, 4, 2))
         self.layers[add_name] = add
         self.layers[drop_name] = add
@@ -1163,14 +1131,11 @@ class vgg16_convs(Network):
             c_i = int(xs[src].shape[-1])
             if tuple(wa.shape[1:]) != (c_i, 1, 1) or tuple(wb.shape[1:]) != (c_i, 1, 1) or wa.shape[0] % 64 or wb.shape[0] % 64:
                 return False
-            key = tuple((t.data_ptr(), t._version) for t in (wa, wb, ba, bb))
-            hit = self._head_wt.get(('merged', src))
-            if hit is None or hit[0] != key:
-                hit = (key, torch.cat([wa.detach().reshape(wa.shape[0], c_i), wb.detach().reshape(wb.shape[0], c_i)]).contiguous(),
-                       torch.cat([ba.detach(), bb.detach()]).contiguous())
-                self._head_wt[('merged', src)] = hit
+            wcat, bcat = self._derived(("merged", src), (wa, wb, ba, bb), lambda: (
+                torch.cat([wa.detach().reshape(wa.shape[0], c_i), wb.detach().reshape(wb.shape[0], c_i)]).contiguous(),
+                torch.cat([ba.detach(), bb.detach()]).contiguous()))
             B_, h, w_ = xs[src].shape[:3]
-            ya, yb = ops.fc_rows_split(xs[src].reshape(-1, c_i), hit[1], hit[2], wa.shape[0], relu_a=True, relu_b=False)
+            ya, yb = ops.fc_rows_split(xs[src].reshape(-1, c_i), wcat, bcat, wa.shape[0], relu_a=True, relu_b=False)
             self.layers[na] = ya.view(B_, h, w_, wa.shape[0])
             self.layers[nb] = yb.view(B_, h, w_, wb.shape[0])
         return True

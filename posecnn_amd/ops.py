@@ -427,10 +427,10 @@ def conv3x3_c3_winograd43(x, weights, bias, relu=True, groups=1):
     return v
 
 
-def conv3x3_c3_winograd43_raw(color_bgr, depth, weights, bias, relu=True, pixel_means=None):
-    """conv3x3_c3_winograd43 on the frames as the sensor delivers them: color_bgr uint8 [B,H,W,3] (or None), depth uint16
-    [B,H,W] (or None); the blobs of lib/fcn/test.py:56-74 are formed inside the kernel, bit for bit. Colour frames first
-    (filter set 0), depth frames after (next set): weights [sets,3,3,3,Cout], bias [sets,Cout]. Returns V [36, T, Cout]."""
+def _raw_frames(color_bgr, depth, pixel_means):
+    """The checked frames of the two raw-frame entries: color_bgr uint8 [B,H,W,3] (or None), depth uint16 [B,H,W] or
+    [B,H,W,1] (or None). Returns (c, nc, d, nd, H, W, device, means): the contiguous tensors with their frame counts and
+    the pixel means (config.PIXEL_MEANS unless given) as the c_double[3] the C entries take."""
     from .config import PIXEL_MEANS
     c = _dev(color_bgr, "color_bgr", torch.uint8) if color_bgr is not None else None
     d = _dev(depth, "depth", torch.uint16) if depth is not None else None
@@ -445,15 +445,21 @@ def conv3x3_c3_winograd43_raw(color_bgr, depth, weights, bias, relu=True, pixel_
     H, W = (c.shape[1], c.shape[2]) if c is not None else (d.shape[1], d.shape[2])
     if c is not None and d is not None and tuple(d.shape[1:]) != (H, W):
         raise ValueError("colour and depth frames must have the same size")
-    nc, nd = (0 if c is None else c.shape[0]), (0 if d is None else d.shape[0])
+    means = (ctypes.c_double * 3)(*[float(m) for m in np.asarray(PIXEL_MEANS if pixel_means is None else pixel_means, dtype=np.float64).reshape(-1)[:3]])
+    return c, (0 if c is None else c.shape[0]), d, (0 if d is None else d.shape[0]), H, W, (c if c is not None else d).device, means
+
+
+def conv3x3_c3_winograd43_raw(color_bgr, depth, weights, bias, relu=True, pixel_means=None):
+    """conv3x3_c3_winograd43 on the frames as the sensor delivers them: color_bgr uint8 [B,H,W,3] (or None), depth uint16
+    [B,H,W] (or None); the blobs of lib/fcn/test.py:56-74 are formed inside the kernel, bit for bit. Colour frames first
+    (filter set 0), depth frames after (next set): weights [sets,3,3,3,Cout], bias [sets,Cout]. Returns V [36, T, Cout]."""
+    c, nc, d, nd, H, W, dev, means = _raw_frames(color_bgr, depth, pixel_means)
     sets = (nc > 0) + (nd > 0)
-    dev = (c if c is not None else d).device
     weights = _dev(weights, "weights", torch.float32)
     bias = _dev(bias, "bias", torch.float32)
     Cout = weights.shape[-1]
     if weights.numel() != sets * 27 * Cout or tuple(weights.shape[-4:]) != (3, 3, 3, Cout) or bias.numel() != sets * Cout:
         raise ValueError("weights must be [sets,3,3,3,Cout] (ky,kx,ci,co) and bias [sets,Cout]")
-    means = (ctypes.c_double * 3)(*[float(x) for x in np.asarray(PIXEL_MEANS if pixel_means is None else pixel_means, dtype=np.float64).reshape(-1)[:3]])
     v = torch.empty((36, (nc + nd) * ((H + 3) // 4) * ((W + 3) // 4), Cout), dtype=torch.float32, device=dev)
     check("pcnn_conv3x3_c3_winograd43_raw_fwd",
           lib().pcnn_conv3x3_c3_winograd43_raw_fwd(_ptr(c), nc, _ptr(d), nd, means, _ptr(weights), _ptr(bias), H, W, Cout,
@@ -491,27 +497,11 @@ def conv1_1_conv1_2_fused(x, w1, b1, ut2, b2, relu1=True, relu2=True, groups=1, 
 def conv1_1_conv1_2_fused_raw(color_bgr, depth, w1, b1, ut2, b2, relu1=True, relu2=True, pixel_means=None, ut2_layout=0):
     """conv1_1_conv1_2_fused on the frames as the sensor delivers them (see conv3x3_c3_winograd43_raw): colour frames first
     (filter set 0), depth frames after (next set)."""
-    from .config import PIXEL_MEANS
-    c = _dev(color_bgr, "color_bgr", torch.uint8) if color_bgr is not None else None
-    d = _dev(depth, "depth", torch.uint16) if depth is not None else None
-    if c is None and d is None:
-        raise ValueError("need colour and / or depth frames")
-    if c is not None and (c.dim() != 4 or c.shape[3] != 3):
-        raise ValueError("color_bgr must be uint8 [B,H,W,3]")
-    if d is not None and d.dim() == 4 and d.shape[3] == 1:
-        d = d.reshape(d.shape[:3])
-    if d is not None and d.dim() != 3:
-        raise ValueError("depth must be uint16 [B,H,W]")
-    H, W = (c.shape[1], c.shape[2]) if c is not None else (d.shape[1], d.shape[2])
-    if c is not None and d is not None and tuple(d.shape[1:]) != (H, W):
-        raise ValueError("colour and depth frames must have the same size")
-    nc, nd = (0 if c is None else c.shape[0]), (0 if d is None else d.shape[0])
+    c, nc, d, nd, H, W, dev, means = _raw_frames(color_bgr, depth, pixel_means)
     sets = (nc > 0) + (nd > 0)
-    dev = (c if c is not None else d).device
     w1, b1, ut2, b2 = (_dev(t, n, torch.float32) for t, n in ((w1, "w1"), (b1, "b1"), (ut2, "ut2"), (b2, "b2")))
     if w1.numel() != sets * 27 * 64 or b1.numel() != sets * 64 or ut2.numel() != sets * 36 * 64 * 64 or b2.numel() != sets * 64:
         raise ValueError("w1 [sets,3,3,3,64], b1 [sets,64], ut2 [sets,36,64,64], b2 [sets,64]")
-    means = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(PIXEL_MEANS if pixel_means is None else pixel_means, dtype=np.float64).reshape(-1)[:3]])
     y = torch.empty((nc + nd, H // 2, W // 2, 64), dtype=torch.float32, device=dev)
     check("pcnn_conv1_1_conv1_2_fused_raw_fwd",
           lib().pcnn_conv1_1_conv1_2_fused_raw_fwd(_ptr(c), nc, _ptr(d), nd, means, _ptr(w1), _ptr(b1), _ptr(ut2), int(ut2_layout),
@@ -716,19 +706,26 @@ def fc_skinny(x, wt, bias, activation="none", num_rows=None):
     return (y, y2) if act == 2 else y
 
 
+def _head_lowres_args(score4, score5, filt, filt_name, planted, stride):
+    """What `head_lowres` and `head_lowres_mfma` check and allocate alike: the tensors on the device, the dimensions of score4,
+    whether score5, the 2-D filter and `planted` fit them (each wrapper adds its own filter shape and raises), and `add`."""
+    score4 = _dev(score4, "score4", torch.float32)
+    score5 = _dev(score5, "score5", torch.float32)
+    filt = _dev(filt, filt_name, torch.float32)
+    pl = _dev(planted, "planted", torch.float32) if planted is not None else None
+    B, h, w, U = score4.shape
+    fits = (tuple(score5.shape) == (B, h // stride, w // stride, U) and filt.dim() == 2
+            and (pl is None or tuple(pl.shape) == tuple(score4.shape)))
+    return score4, score5, filt, pl, B, h, w, U, fits, torch.empty_like(score4)
+
+
 def head_lowres(score4, score5, weights_t, planted=None, kernel=4, stride=2):
     """add = score4 + deconv_{kernel,stride}(score5) [+ planted]; z = add . weights_t (1x1 conv, no bias) in one
     launch. score4 [B,h,w,U], score5 [B,h/stride,w/stride,U], weights_t [U, Cout] -> (add [B,h,w,U], z [B,h,w,Cout])."""
-    score4 = _dev(score4, "score4", torch.float32)
-    score5 = _dev(score5, "score5", torch.float32)
-    weights_t = _dev(weights_t, "weights_t", torch.float32)
-    pl = _dev(planted, "planted", torch.float32) if planted is not None else None
-    B, h, w, U = score4.shape
-    if (tuple(score5.shape) != (B, h // stride, w // stride, U) or weights_t.dim() != 2 or weights_t.shape[0] != U
-            or (pl is not None and tuple(pl.shape) != tuple(score4.shape))):
+    score4, score5, weights_t, pl, B, h, w, U, fits, add = _head_lowres_args(score4, score5, weights_t, "weights_t", planted, stride)
+    if not fits or weights_t.shape[0] != U:
         raise ValueError("score4 [B,h,w,U], score5 [B,h/s,w/s,U], weights_t [U,Cout], planted like score4")
     Cout = weights_t.shape[1]
-    add = torch.empty_like(score4)
     z = torch.empty((B, h, w, Cout), dtype=torch.float32, device=score4.device)
     check("pcnn_head_lowres_fwd", lib().pcnn_head_lowres_fwd(_ptr(score4), _ptr(score5), _ptr(pl), _ptr(weights_t), B, h, w, U, Cout,
                                                             int(kernel), int(stride), _ptr(add), _ptr(z), _stream(score4)))
@@ -748,16 +745,10 @@ def head_lowres_mfma_filter(weights_t):
 def head_lowres_mfma(score4, score5, weights_nk, out_channels, planted=None, kernel=4, stride=2):
     """`head_lowres` for many pixels per launch: the same add (bit-identical `add`), the 1x1 product on the matrix cores.
     weights_nk from `head_lowres_mfma_filter`. U % 16 == 0, out_channels <= 96."""
-    score4 = _dev(score4, "score4", torch.float32)
-    score5 = _dev(score5, "score5", torch.float32)
-    weights_nk = _dev(weights_nk, "weights_nk", torch.float32)
-    pl = _dev(planted, "planted", torch.float32) if planted is not None else None
-    B, h, w, U = score4.shape
+    score4, score5, weights_nk, pl, B, h, w, U, fits, add = _head_lowres_args(score4, score5, weights_nk, "weights_nk", planted, stride)
     Cout = int(out_channels)
-    if (tuple(score5.shape) != (B, h // stride, w // stride, U) or weights_nk.dim() != 2 or weights_nk.shape[1] != U
-            or weights_nk.shape[0] != (Cout + 15) // 16 * 16 or (pl is not None and tuple(pl.shape) != tuple(score4.shape))):
+    if not fits or tuple(weights_nk.shape) != ((Cout + 15) // 16 * 16, U):
         raise ValueError("score4 [B,h,w,U], score5 [B,h/s,w/s,U], weights_nk [ceil(Cout/16)*16, U], planted like score4")
-    add = torch.empty_like(score4)
     z = torch.empty((B, h, w, Cout), dtype=torch.float32, device=score4.device)
     check("pcnn_head_lowres_mfma_fwd", lib().pcnn_head_lowres_mfma_fwd(_ptr(score4), _ptr(score5), _ptr(pl), _ptr(weights_nk), B, h, w, U, Cout,
                                                                       int(kernel), int(stride), _ptr(add), _ptr(z), _stream(score4)))

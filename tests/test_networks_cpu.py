@@ -218,3 +218,138 @@ def test_load_keeps_depth_tower_weights_and_drops_constant_deconv_filters():
     trained = tf_filter.copy(); trained[3, 3, 0, 1] = 0.01                   # somebody fine-tuned the filter
     net.load({"upscore": {"weights": trained}})
     assert "upscore/weights" in net.vars and not net.fused_heads           # literal op order, dense conv_transpose
+
+
+# the variables of a lazily initialised network in creation order, as lib/networks/vgg16_convs.py:79-193 creates them
+COLOR_TOWER_VARS = [
+    "conv1_1/weights", "conv1_1/biases", "conv1_2/weights", "conv1_2/biases",
+    "conv2_1/weights", "conv2_1/biases", "conv2_2/weights", "conv2_2/biases",
+    "conv3_1/weights", "conv3_1/biases", "conv3_2/weights", "conv3_2/biases",
+    "conv3_3/weights", "conv3_3/biases", "conv4_1/weights", "conv4_1/biases",
+    "conv4_2/weights", "conv4_2/biases", "conv4_3/weights", "conv4_3/biases",
+    "conv5_1/weights", "conv5_1/biases", "conv5_2/weights", "conv5_2/biases",
+    "conv5_3/weights", "conv5_3/biases",
+]
+DEPTH_TOWER_VARS = [
+    "conv1_1_p/weights", "conv1_1_p/biases", "conv1_2_p/weights", "conv1_2_p/biases",
+    "conv2_1_p/weights", "conv2_1_p/biases", "conv2_2_p/weights", "conv2_2_p/biases",
+    "conv3_1_p/weights", "conv3_1_p/biases", "conv3_2_p/weights", "conv3_2_p/biases",
+    "conv3_3_p/weights", "conv3_3_p/biases", "conv4_1_p/weights", "conv4_1_p/biases",
+    "conv4_2_p/weights", "conv4_2_p/biases", "conv4_3_p/weights", "conv4_3_p/biases",
+    "conv5_1_p/weights", "conv5_1_p/biases", "conv5_2_p/weights", "conv5_2_p/biases",
+    "conv5_3_p/weights", "conv5_3_p/biases",
+]
+HEAD_VARS = [
+    "score_conv5/weights", "score_conv5/biases", "score_conv4/weights", "score_conv4/biases",
+    "score/weights", "score/biases", "score_conv5_vertex/weights", "score_conv5_vertex/biases",
+    "score_conv4_vertex/weights", "score_conv4_vertex/biases", "vertex_pred/weights", "vertex_pred/biases",
+    "fc6/weights", "fc6/biases", "fc7/weights", "fc7/biases",
+    "fc8/weights", "fc8/biases",
+]
+VARS_IN_ORDER = {"COLOR": COLOR_TOWER_VARS + HEAD_VARS, "RGBD": COLOR_TOWER_VARS + DEPTH_TOWER_VARS + HEAD_VARS}
+
+
+@pytest.mark.parametrize("fmt", ["COLOR", "RGBD"])
+def test_lazily_created_variables_come_in_the_reference_order(fmt):
+    """The seeded generator makes creation order part of the behaviour: a lazily initialised network creates its variables
+    in the order of lib/networks/vgg16_convs.py:79-193 — the colour tower, the depth tower (RGBD), score_conv5, score_conv4,
+    score, the vertex head, fc6-8 (the constant deconv filters are no variables here) — weights before biases in every
+    layer (network.py:169-185,409-411)."""
+    net = vgg16_convs_cpu(fmt, 22, 64, (1.0,), 1.0, -1.0, vertex_reg_2d=True, pose_reg=True, trainable=False, is_train=False)
+    K = config.DEMO_INTRINSICS.copy()
+    data = torch.from_numpy(np.random.default_rng(0).standard_normal((1, 16, 16, 3)).astype(F))
+    feed = {"data": data, "gt_label_2d": torch.ones((1, 16, 16), dtype=torch.int32), "keep_prob": 1.0, "poses": torch.zeros((1, 13)),
+            "extents": torch.from_numpy(config.LOV_EXTENTS), "meta_data": torch.from_numpy(config.make_meta_data(K)).reshape(1, 1, 1, 48)}
+    if fmt == "RGBD":
+        feed["data_p"] = data.clone()
+    with torch.no_grad():
+        net.run(feed)
+    assert list(net.vars) == VARS_IN_ORDER[fmt]
+
+
+# (rows, dim, num_out, padded_width) -> route, for a CUDA input with a device-side row count and no autograd. The skinny
+# kernel takes 1..32 rows of a 2-D input whose width is a multiple of 16; the row kernel takes dim % 64 == 0, dim >= 128 and
+# num_out % 64 == 0 — num_out % 4 == 0 when the caller pads the filter (fc_tanh).
+FC_ROUTES = {
+    (None, 112, 64, False): "addmm", (None, 112, 64, True): "addmm", (None, 112, 88, False): "addmm", (None, 112, 88, True): "addmm",
+    (None, 128, 64, False): "rows", (None, 128, 64, True): "rows", (None, 128, 88, False): "addmm", (None, 128, 88, True): "rows",
+    (None, 4096, 64, False): "rows", (None, 4096, 64, True): "rows", (None, 4096, 88, False): "addmm", (None, 4096, 88, True): "rows",
+    (1, 112, 64, False): "skinny", (1, 112, 64, True): "skinny", (1, 112, 88, False): "skinny", (1, 112, 88, True): "skinny",
+    (1, 128, 64, False): "skinny", (1, 128, 64, True): "skinny", (1, 128, 88, False): "skinny", (1, 128, 88, True): "skinny",
+    (1, 4096, 64, False): "skinny", (1, 4096, 64, True): "skinny", (1, 4096, 88, False): "skinny", (1, 4096, 88, True): "skinny",
+    (32, 112, 64, False): "skinny", (32, 112, 64, True): "skinny", (32, 112, 88, False): "skinny", (32, 112, 88, True): "skinny",
+    (32, 128, 64, False): "skinny", (32, 128, 64, True): "skinny", (32, 128, 88, False): "skinny", (32, 128, 88, True): "skinny",
+    (32, 4096, 64, False): "skinny", (32, 4096, 64, True): "skinny", (32, 4096, 88, False): "skinny", (32, 4096, 88, True): "skinny",
+    (33, 112, 64, False): "addmm", (33, 112, 64, True): "addmm", (33, 112, 88, False): "addmm", (33, 112, 88, True): "addmm",
+    (33, 128, 64, False): "rows", (33, 128, 64, True): "rows", (33, 128, 88, False): "addmm", (33, 128, 88, True): "rows",
+    (33, 4096, 64, False): "rows", (33, 4096, 64, True): "rows", (33, 4096, 88, False): "addmm", (33, 4096, 88, True): "rows",
+}
+
+
+def test_fc_route_table():
+    """`Network._fc_route` is the one routing predicate of `fc`, `fc_tanh` and `fc_masks_dead_rows`: written out as a table."""
+    net = Tiny(device="cpu", trainable=False)
+    assert len(FC_ROUTES) == 4 * 3 * 2 * 2
+    for (rows, dim, num_out, padded), want in FC_ROUTES.items():
+        got = net._fc_route(True, rows, dim, num_out, False, True, padded_width=padded)
+        assert got == want, (rows, dim, num_out, padded, got)
+    # the three causes that send everything to the framework, whatever the shapes
+    for padded in (False, True):
+        assert net._fc_route(False, 8, 128, 64, False, True, padded_width=padded) == "addmm"    # a CPU tensor
+        assert net._fc_route(True, 8, 128, 64, True, True, padded_width=padded) == "addmm"     # recorded for autograd
+        assert net._fc_route(True, 8, 128, 64, False, False, padded_width=padded) == "addmm"    # no device-side row count
+    net.fc_skinny = False   # the switch: few rows go where many rows go
+    assert net._fc_route(True, 8, 128, 64, False, True) == "rows" and net._fc_route(True, 8, 112, 64, False, True) == "addmm"
+
+
+def test_derived_cache_validity():
+    """`Network._derived` — the one place that decides whether a tensor derived from variables is still good: a hit on a
+    repeat; a rebuild after an in-place update, after the variable is replaced by another object (even one with equal
+    values), and when `extra` changes; and the entry keeps its sources alive, so their addresses cannot be reused under it."""
+    import gc
+    import weakref
+    net = Tiny(device="cpu", trainable=False)
+    w, b = torch.arange(6.0).reshape(2, 3), torch.ones(3)
+    builds = []
+
+    def build_from(*src):
+        def build():
+            builds.append(len(builds))
+            return src[0].t() + src[1].reshape(-1, 1) if len(src) > 1 else src[0].t().contiguous()
+        return build
+
+    first = net._derived("slot", (w, b), build_from(w, b), 4)
+    assert builds == [0] and torch.equal(first, w.t() + b.reshape(-1, 1))
+    assert net._derived("slot", (w, b), build_from(w, b), 4) is first and builds == [0]              # a repeat: hit
+    assert net._derived("other", (w,), build_from(w)) is not first and builds == [0, 1]              # slots are independent
+    assert net._derived("slot", (w, b), build_from(w, b), 4) is first and len(builds) == 2
+    b.mul_(2.0)                                                                                      # in place: same object, new version
+    second = net._derived("slot", (w, b), build_from(w, b), 4)
+    assert len(builds) == 3 and torch.equal(second, w.t() + b.reshape(-1, 1)) and not torch.equal(second, first)
+    assert net._derived("slot", (w, b), build_from(w, b), 4) is second and len(builds) == 3
+    w2 = w.clone()                                                                                   # another object, equal values, version 0 again
+    third = net._derived("slot", (w2, b), build_from(w2, b), 4)
+    assert len(builds) == 4 and third is not second
+    assert net._derived("slot", (w2, b), build_from(w2, b), 4) is third and len(builds) == 4
+    fourth = net._derived("slot", (w2, b), build_from(w2, b), 2)                                     # `extra` changed
+    assert len(builds) == 5 and fourth is not third
+    assert net._derived("slot", (w2, b), build_from(w2, b), 2) is fourth and len(builds) == 5
+    assert net._derived("slot", (w2,), build_from(w2), 2) is not fourth and len(builds) == 6         # fewer sources is another entry
+    # the entry pins its sources: dropping every outside reference does not free them
+    v = torch.full((4,), 3.0)
+    ref = weakref.ref(v)
+    net._derived("pinned", (v,), lambda: None)
+    del v
+    gc.collect()
+    assert ref() is not None
+    net._derived("pinned", (w,), lambda: None)   # replaced entry: the old source goes
+    gc.collect()
+    assert ref() is None
+    # ... and so do the entries of the variables that load() replaces
+    net.vars = {"fc/weights": torch.ones((3, 2)), "fc/biases": torch.zeros(2), "other/biases": torch.zeros(1)}
+    ref = weakref.ref(net.vars["fc/weights"])
+    net._derived("loaded", (net.vars["fc/weights"], net.vars["fc/biases"]), lambda: None)
+    kept = net._derived("kept", (net.vars["other/biases"],), lambda: torch.zeros(1))
+    net.load({"fc": {"weights": np.ones((3, 2), F)}})
+    gc.collect()
+    assert ref() is None and net._derived("kept", (net.vars["other/biases"],), lambda: None) is kept
