@@ -60,7 +60,10 @@ NUM_MODEL_POINTS = 2620  # min over data/LOV/models/*/points.xyz (lov.py:141-158
 class TestConfig:
     """The knobs `vgg16_convs` is built with for tools/demo.py / tools/test_net.py."""
     __test__ = False  # not a pytest class
-    input_format: str = "COLOR"          # lov_color_2d.yml:2
+    # lov_color_2d.yml:2. The reference's cfg.INPUT values (lib/fcn/test.py:161-169): "COLOR" the BGR frame; "RGBD" a
+    # second tower on the depth blob; "DEPTH" the depth blob alone; "NORMAL" the bilateral-filtered surface-normal
+    # image of the depth frame (ops.normal_image; needs the frame's intrinsic_matrix and factor_depth).
+    input_format: str = "COLOR"
     num_classes: int = 22                # lov_color_2d.yml:14
     num_units: int = 64                  # lov_color_2d.yml:15
     scales_base: tuple = (1.0,)          # lov_color_2d.yml:39

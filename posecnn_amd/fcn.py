@@ -98,7 +98,8 @@ def nms(dets, thresh):
 def _get_image_blob(im, im_depth, scale=1.0):
     """lib/fcn/test.py:37-110 for INPUT in {COLOR, RGBD} and SCALES_BASE = (1.0,):
     BGR float32 minus PIXEL_MEANS; depth tower input = clip(depth/2000, 0, 1)*255 tiled to 3
-    channels minus the same means. Returns (blob[1,H,W,3], blob_depth[1,H,W,3], im_scale)."""
+    channels minus the same means. Returns (blob[1,H,W,3], blob_depth[1,H,W,3], im_scale).
+    INPUT in {DEPTH, NORMAL} do not come through here: `_depth_frame_input` hands the network the raw frame."""
     assert scale == 1.0, "only SCALES_BASE = (1.0,) is on the demo/test path (lov_color_2d.yml:39)"
     im_orig = im.astype(np.float32, copy=True)
     im_orig -= PIXEL_MEANS
@@ -126,6 +127,24 @@ def combine_poses(rois, poses_init, poses_pred):
     return rois, poses, keep
 
 
+def _depth_frame_input(input_format, im_depth, meta_data, device):
+    """The `data` of the depth-only input modes (lib/fcn/test.py:166-169), on the device, as a raw frame the first
+    kernel turns into the blob (ops.conv1_1_conv1_2_fused_raw subtracts PIXEL_MEANS):
+    'DEPTH': the uint16 depth frame itself [1,H,W,1] -> clip(d / 2000, 0, 1) * 255 tiled to 3 channels (:70-74);
+    'NORMAL': ops.normal_image of it, uint8 [1,H,W,3] (:80-96: K as float32, depth / factor_depth, gpu_normals with
+    cutoff 20, uint8, channels (2, 1, 0), bilateralFilter(9, 75, 75))."""
+    im_depth = np.asarray(im_depth)
+    if im_depth.dtype != np.uint16 or im_depth.ndim != 2:
+        raise TypeError("im_depth must be the uint16 [H,W] depth frame as read (got %s %s)" % (im_depth.dtype, im_depth.shape))
+    depth = torch.from_numpy(np.ascontiguousarray(im_depth)[np.newaxis]).to(device)
+    if input_format == "DEPTH":
+        return depth.unsqueeze(-1)
+    K = np.array(meta_data["intrinsic_matrix"], dtype=np.float64).astype(np.float32)
+    intrinsics = torch.from_numpy(np.array([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]]], dtype=np.float32)).to(device)
+    factor = float(np.asarray(meta_data["factor_depth"]).reshape(-1)[0])
+    return ops.normal_image(depth, intrinsics, factor_depth=factor, depth_cutoff=20.0, d=9, sigma_color=75.0, sigma_space=75.0)
+
+
 def _feed(net, data, data_p, K, extents, points, symmetry, num_classes, device):
     B, H, W, _ = data.shape
     meta = np.stack([make_meta_data(K)] * B).reshape(B, 1, 1, 48)
@@ -149,10 +168,16 @@ def _feed(net, data, data_p, K, extents, points, symmetry, num_classes, device):
 def im_segment_single_frame(net, im, im_depth, meta_data, extents, points, symmetry, num_classes, device="cuda"):
     """lib/fcn/test.py:113-239 (TEST.VERTEX_REG_2D and TEST.POSE_REG set, as in lov_color_2d.yml).
     `im` is BGR uint8 (OpenCV order), already padded to a multiple of 16 by the caller (:1870).
+    `net.input_format` selects the input (:161-169): 'COLOR' the colour blob, 'RGBD' colour + depth blob, 'DEPTH' the
+    depth blob alone, 'NORMAL' the filtered normal image of the depth frame (needs meta_data["factor_depth"]); the last
+    two do not read `im`.
     Returns (labels_2d[H,W] int32, probs[H,W,C], vertex_pred[H,W,3C], rois[R,7], poses[R,7])."""
-    blob, blob_depth, im_scale = _get_image_blob(im, im_depth)
+    if net.input_format in ("DEPTH", "NORMAL"):
+        blob, data_p, im_scale = _depth_frame_input(net.input_format, im_depth, meta_data, torch.device(device)), None, 1.0
+    else:
+        blob, blob_depth, im_scale = _get_image_blob(im, im_depth)
+        data_p = blob_depth if net.input_format == "RGBD" else None
     K = np.array(meta_data["intrinsic_matrix"], dtype=np.float64) * im_scale
-    data_p = blob_depth if net.input_format == "RGBD" else None
     feed = _feed(net, blob, data_p, K, extents, points, symmetry, num_classes, torch.device(device))
     net.run(feed)
     g = lambda n: net.get_output(n).detach().cpu().numpy()
@@ -181,7 +206,9 @@ class Detections(object):
 def im_segment_batch(net, data, K, extents, points, symmetry, data_p=None, planted=None, feed_cache=None,
                      with_losses=False, gt_poses=None, strict_reference=False, frame_offset=None):
     """B frames, one pass, no host synchronisation. `data` is the mean-subtracted BGR blob
-    [B,H,W,3] already on the device. Returns `Detections` (device tensors; rows past count are 0).
+    [B,H,W,3] already on the device — or a raw frame batch the first kernel forms the blob of: uint8 [B,H,W,3] (camera
+    frames, or the `ops.normal_image` of the depth frames for a 'NORMAL' network) or uint16 depth [B,H,W,1] (a 'DEPTH'
+    network). Returns `Detections` (device tensors; rows past count are 0).
 
     Capacity: the reference op keeps MAX_ROI / B maxima per image when handed a batch
     (hough_voting_gpu_op.cu.cc:733) — but its test loop feeds one frame at a time

@@ -23,6 +23,7 @@ __all__ = [
     "average_distance_loss", "backproject", "softmax_argmax", "deconv_bilinear", "bias_act_",
     "hough_voting_grad", "hard_label_grad", "hough_rows_capacity",
     "upscore_softmax_argmax", "Workspace", "vertex_targets", "smooth_l1_loss_vertex_gt",
+    "depth_normals", "bilateral_filter_u8", "normal_image", "bilateral_tables",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1134,3 +1135,108 @@ def backproject(data, label, depth, meta_data, label_3d, grid_size, kernel_size,
     if label_3d.dim() != 5:
         raise ValueError("label 3D must be 5-dimensional")   # :344-345
     return _BackprojectFn.apply(data, label, depth, meta_data, label_3d, grid_size, kernel_size, threshold)
+
+
+# ------------------------------------------------------------------------------------------------
+# input front end (include/posecnn_hip_frontend.h): the network input of cfg.INPUT = 'NORMAL'
+_bilateral_cache = {}
+
+
+def bilateral_tables(d, sigma_color, sigma_space, device=None):
+    """The two weight tables of the 8-bit 3-channel bilateral filter as OpenCV's scalar code builds them, with numpy on
+    the host: color_weight f32 [768], entry i = float32(exp(i i (-0.5 / sigma_color^2))); space_weight f32 [K] and
+    offsets int32 [K,2], one row (i, j) per tap of [-r, r]^2 (r = d // 2, i outer, j inner) with
+    rho = sqrt(float64(i i + j j)) <= r, entry = float32(exp(rho rho (-0.5 / sigma_space^2))); a sigma <= 0 counts as 1.
+    Returns (color_weight, space_weight, offsets): numpy arrays, or with `device` the two tables as tensors there
+    (cached per device and parameter triple) and the offsets as numpy."""
+    d = int(d)
+    if d < 3 or d > 15 or d % 2 == 0:
+        raise ValueError("d must be odd, 3 <= d <= 15 (got %d)" % d)
+    if device is not None:
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:   # 'cuda' and 'cuda:0' are one cache entry
+            device = torch.device("cuda", torch.cuda.current_device())
+    key = (None if device is None else str(device), d, float(sigma_color), float(sigma_space))
+    if key not in _bilateral_cache:
+        host = _bilateral_cache.get((None,) + key[1:])
+        if host is None:
+            sc = float(sigma_color) if sigma_color > 0 else 1.0
+            ss = float(sigma_space) if sigma_space > 0 else 1.0
+            r = d // 2
+            i = np.arange(768, dtype=np.float64)
+            color = np.exp(i * i * (-0.5 / (sc * sc))).astype(np.float32)
+            offsets = np.array([(a, b) for a in range(-r, r + 1) for b in range(-r, r + 1)
+                                if np.sqrt(np.float64(a * a + b * b)) <= r], dtype=np.int32)
+            rho = np.sqrt((offsets.astype(np.float64) ** 2).sum(axis=1))
+            space = np.exp(rho * rho * (-0.5 / (ss * ss))).astype(np.float32)
+            host = _bilateral_cache[(None,) + key[1:]] = (color, space, offsets)
+        if device is not None:
+            _bilateral_cache[key] = (torch.from_numpy(host[0]).to(device), torch.from_numpy(host[1]).to(device), host[2])
+    return _bilateral_cache[key]
+
+
+def _depth_args(depth, intrinsics, factor_depth):
+    """The checked depth inputs of include/posecnn_hip_frontend.h: depth f32 [B,H,W] in metres (factor_depth None) or
+    uint16 [B,H,W] with its factor_depth; intrinsics f32 [B,4] rows (fx, fy, cx, cy).
+    Returns (depth_f32 | None, depth_u16 | None, factor, intrinsics, B, H, W)."""
+    if not isinstance(depth, torch.Tensor):
+        raise TypeError("depth must be a torch.Tensor")
+    raw = depth.dtype == torch.uint16
+    depth = _dev(depth, "depth", torch.uint16 if raw else torch.float32)
+    intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+    if depth.dim() == 4 and depth.shape[3] == 1:
+        depth = depth.reshape(depth.shape[:3])
+    if depth.dim() != 3:
+        raise ValueError("depth must be [B,H,W] (got %s)" % (tuple(depth.shape),))
+    if raw and factor_depth is None:
+        raise ValueError("a uint16 depth frame needs its factor_depth")
+    if not raw and factor_depth is not None:
+        raise ValueError("factor_depth goes with a uint16 depth frame; a float32 frame is in metres")
+    B, H, W = depth.shape
+    if tuple(intrinsics.shape) != (B, 4):
+        raise ValueError("intrinsics must be [B,4] rows (fx, fy, cx, cy) with B = %d (got %s)" % (B, tuple(intrinsics.shape)))
+    return (None if raw else depth), (depth if raw else None), (float(factor_depth) if raw else 0.0), intrinsics, B, H, W
+
+
+def depth_normals(depth, intrinsics, depth_cutoff=20.0, factor_depth=None):
+    """gpu_normals (lib/normals/compute_normals.cu:30-101) of B depth frames, one IEEE rounding per operation:
+    depth f32 [B,H,W] in metres, or uint16 [B,H,W] with `factor_depth` (z = float32(d) / factor_depth);
+    intrinsics f32 [B,4] rows (fx, fy, cx, cy). Returns nmap f32 [B,H,W,3]; NaN (0x7fffffff) where the reference's is."""
+    f32, u16, factor, intr, B, H, W = _depth_args(depth, intrinsics, factor_depth)
+    nmap = torch.empty((B, H, W, 3), dtype=torch.float32, device=intr.device)
+    check("pcnn_depth_normals_fwd",
+          lib().pcnn_depth_normals_fwd(_ptr(f32), _ptr(u16), factor, _ptr(intr), B, H, W, float(depth_cutoff), _ptr(nmap),
+                                       _stream(nmap)))
+    return nmap
+
+
+def bilateral_filter_u8(image, d=9, sigma_color=75.0, sigma_space=75.0):
+    """cv2.bilateralFilter(image, d, sigma_color, sigma_space) of uint8 [B,H,W,3] frames (border reflect-101) with the
+    arithmetic of OpenCV's scalar code (include/posecnn_hip_frontend.h). Returns uint8 [B,H,W,3]."""
+    image = _dev(image, "image", torch.uint8)
+    if image.dim() != 4 or image.shape[3] != 3:
+        raise ValueError("image must be uint8 [B,H,W,3] (got %s)" % (tuple(image.shape),))
+    color, space, _ = bilateral_tables(d, sigma_color, sigma_space, image.device)
+    B, H, W, _ = image.shape
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=image.device)
+    check("pcnn_bilateral_u8c3_fwd",
+          lib().pcnn_bilateral_u8c3_fwd(_ptr(image), B, H, W, int(d), _ptr(color), _ptr(space), space.numel(), _ptr(out),
+                                        _stream(out)))
+    return out
+
+
+def normal_image(depth, intrinsics, factor_depth=None, depth_cutoff=20.0, d=9, sigma_color=75.0, sigma_space=75.0):
+    """The uint8 image lib/fcn/test.py:89-94 forms under cfg.INPUT = 'NORMAL', in one kernel:
+    bilateral_filter_u8(uint8(127.5 depth_normals(depth) + 127.5)[..., (2, 1, 0)], d, sigma_color, sigma_space); d = 0
+    leaves the filter out. Arguments as `depth_normals`. Returns uint8 [B,H,W,3], which the network takes as `data`
+    (the first kernel subtracts PIXEL_MEANS: ops.conv1_1_conv1_2_fused_raw)."""
+    f32, u16, factor, intr, B, H, W = _depth_args(depth, intrinsics, factor_depth)
+    color, space, taps = None, None, 0
+    if int(d) != 0:
+        color, space, _ = bilateral_tables(d, sigma_color, sigma_space, intr.device)
+        taps = space.numel()
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=intr.device)
+    check("pcnn_normal_image_fwd",
+          lib().pcnn_normal_image_fwd(_ptr(f32), _ptr(u16), factor, _ptr(intr), B, H, W, float(depth_cutoff), int(d),
+                                      _ptr(color), _ptr(space), taps, _ptr(out), _stream(out)))
+    return out
