@@ -178,6 +178,26 @@ def _hough_lowres(name, B, H, W, C, n_obj, k, s, lt):
     add(name, ("pcnn_hough_voting_lowres_fwd",), make, run, check)
 
 
+def _hough_threshold_case(name, case_id):
+    """A case of tests/thresholds.py: wave_cell_data flushes its LDS strip twice for the second maximum."""
+    import thresholds as TH
+    case = TH.CASE[case_id]
+
+    def run(c):
+        from posecnn_amd import ops
+        out = ops.hough_voting_gpu_padded(c.e("label"), c.e("vertex"), c.e("ext"), c.e("meta"), None, 0, case["vote_thr"],
+                                          TH.HOUGH_PER_THR, case["skip"], label_threshold=case["label_thr"])
+        return dict(zip(HOUGH_NAMES, out))
+
+    def check(d, o):
+        want = TH.reference(case_id)
+        for n in HOUGH_NAMES:
+            same(o[n], want[n], n)
+        assert int(o["num_rois"][1]) >= 2
+    add(name, ("pcnn_hough_voting_fwd",), lambda: dict(TH.build(case_id)), run, check)
+
+
+_hough_threshold_case("hough_strip_flushes", "hough_wcd_2000")
 _hough_lowres("hough_lowres_k4s2", 3, 120, 160, 8, 3, 4, 2, 60)
 _hough_lowres("hough_lowres_k16s8", 1, 96, 136, 6, 2, 16, 8, 40)
 
@@ -344,6 +364,7 @@ def _adl(name, R, cap, C, P, margin, backward=False):
 _adl("adl_count0", 0, 4, 22, 700, 0.01)
 _adl("adl_count_cap", 16, 16, 22, 700, 0.01, backward=True)
 _adl("adl_7_of_16", 7, 16, 22, 2620, 0.0)
+_adl("adl_second_sum_round", 5, 8, 22, 3073, 0.0)       # P > ADL_SUM_TILE_MAX: a second staged round of one term; margin 0 keeps it live
 
 
 # =====================================================================================================================

@@ -79,6 +79,29 @@ def test_hough_voting_matches_reference_kernels(ref, vote_thr, per_thr, skip):
     bits_equal(whs, got[6], "hough_space (every cell)")
 
 
+# The flush-sized frames of tests/thresholds.py: one cell with more voters than wave_cell_data's strip holds twice over
+# (vote_threshold > 0) / than hv_select_kernel's buffer holds (max_element path), every voter with a depth of its own, so
+# the cell's depth is an ordered f32 sum that the oracle must take in the reference's order. The GPU cases there lean on
+# the oracle in exactly these regimes.
+@pytest.mark.parametrize("case_id", ["hough_wcd_2000", "hough_sel_5000"])
+def test_hough_flush_sized_frames_match_reference_kernels(ref, case_id):
+    import thresholds as TH
+    case, d = TH.CASE[case_id], TH.build(case_id)
+    want, whs = ref_hough(ref, d["label"], d["vertex"], d["ext"], d["meta"], None, 0, case["vote_thr"], TH.HOUGH_PER_THR, case["skip"],
+                          case["label_thr"])
+    got = oracle.hough_voting(d["label"], d["vertex"], d["ext"], d["meta"], None, 0, case["vote_thr"], TH.HOUGH_PER_THR, case["skip"],
+                              label_thr=case["label_thr"], padded=True, want_hs=True)
+    n = int(want[5][1])
+    assert want[0][:n, 6].max() == max(b[2] for b in case["blobs"]) > 1920
+    for cls in {b[0] for b in case["blobs"]}:                          # a depth of its own per voter
+        depths = d["vertex"][d["label"] == cls][:, 3 * cls + 2]
+        assert len(np.unique(depths)) > 0.99 * len(depths)
+    assert len(set(want[1][:n, 6])) == n and not (want[1][:n, 6] == 1).any()
+    for name, w, g in zip(("top_box", "top_pose", "top_target", "top_weight", "top_domain", "num_rois"), want, got[:6]):
+        bits_equal(w, g, name)
+    bits_equal(whs, got[6], "hough_space")
+
+
 def test_hough_voting_train_mode_matches_reference_kernels(ref):
     label, vertex, meta, fr = small_frames(210, 2, 96, 128, 6, 3)
     ext = config.LOV_EXTENTS[:6] * 0.6
@@ -175,15 +198,13 @@ def test_hard_label_matches_reference_kernels(ref):
     bits_equal(out, oracle.hard_label(prob, gt, 0.4), "hard_label")
 
 
-@pytest.mark.parametrize("margin", [0.0, 0.01])
-def test_average_distance_matches_reference_kernels(ref, margin):
+def _average_distance_pin(ref, margin, C, P, R, no_target=3):
     rng = np.random.default_rng(5)
-    C, P, R = 6, 150, 7
     pts = synth.make_model_points(C, P, extents=config.LOV_EXTENTS[:C] + 0.05)
     sym = np.array([0, 0, 1, 0, 1, 0], F)
     pred = np.zeros((R, 4 * C), F); tgt = np.zeros((R, 4 * C), F); wgt = np.zeros((R, 4 * C), F)
     for n in range(R):
-        if n == 3:
+        if n == no_target:
             continue
         c = 1 + n % 5
         pred[n, 4 * c:4 * c + 4] = np.tanh(rng.standard_normal(4)); tgt[n, 4 * c:4 * c + 4] = synth.random_unit_quats(rng, 1)[0]
@@ -191,11 +212,19 @@ def test_average_distance_matches_reference_kernels(ref, margin):
     loss = np.zeros(1, F); diff = np.zeros((R, 4 * C), F)
     ref.ref_average_distance(p(pred), p(tgt), p(wgt), p(pts), p(sym), R, C, P, c_float(margin), p(loss), p(diff))
     gl, gd = oracle.average_distance(pred, tgt, wgt, pts, sym, margin)
-    assert loss[0] > 0
+    assert loss[0] > 0 and sum(sym[1 + n % 5] > 0 for n in range(R) if n != no_target) == 2
     bits_equal(loss, gl, "loss"); bits_equal(diff, gd, "bottom_diff")
     g = np.array([2.5], F); out = np.empty_like(diff)
     ref.ref_average_distance_bwd(p(g), p(diff), diff.size, p(out))
     bits_equal(out, oracle.average_distance_bwd(g, gd), "grad")
+
+
+@pytest.mark.parametrize("margin", [0.0, 0.01])
+def test_average_distance_matches_reference_kernels(ref, margin):
+    _average_distance_pin(ref, margin, 6, 150, 7)
+    # P > 3072: the rows whose sums the kernel takes in more than one staged round (tests/thresholds.py, adl_sum_tile);
+    # rows 1 and 3 are of the symmetric classes 2 and 4, row 2 has no target
+    _average_distance_pin(ref, margin, 6, 3073, 5, no_target=2)
 
 
 def test_backproject_matches_reference_kernels(ref):
