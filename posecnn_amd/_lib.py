@@ -1,5 +1,5 @@
-"""ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h, include/posecnn_hip_train.h and
-include/posecnn_hip_frontend.h).
+"""ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h, include/posecnn_hip_train.h,
+include/posecnn_hip_frontend.h and include/posecnn_hip_synth.h).
 
 This is the Python-side analogue of the reference's ``tf.load_op_library('<op>.so')`` stubs
 (lib/hough_voting_gpu_layer/hough_voting_gpu_op.py:4-7 and siblings). The library is built
@@ -130,6 +130,14 @@ FRONTEND_SIGNATURES = {
     "pcnn_normal_image_fwd": (c_int, [_P, _P, c_float, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, c_int, _P, _P]),
 }
 
+# the synthetic-scene entries of include/posecnn_hip_synth.h (same library, same ABI version)
+SYNTH_SIGNATURES = {
+    "pcnn_synth_scene_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "pcnn_synth_scene_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P, _P, _P, c_int, _P, _P,
+                                     c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_int,
+                                     _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 
 def profile_enable(on=True):
     """Bracket every library kernel launch with HIP events on its launch stream."""
@@ -175,7 +183,8 @@ def lib():
         # (round 6: `build()` followed by `smoke()` in one process did exactly that). So torch's goes in first, always.
         import torch  # noqa: F401
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) +\
+                list(SYNTH_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args

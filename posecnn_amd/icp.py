@@ -317,6 +317,8 @@ class Synthesizer:
         self.width = self.height = None
         self.last = []                # per processed ROI: hits / pairs of each hypothesis and the chosen one
         self._streams = []            # one per object of a frame (created on first use)
+        self.synthesis_seed = 0       # render_python: seed of the scene sampler (created on first use)
+        self._bank = self._sampler = None
 
     def setup(self, width, height):
         self.width, self.height = int(width), int(height)
@@ -325,6 +327,56 @@ class Synthesizer:
                 raise ValueError("Synthesizer needs model_file or meshes")
             with open(self.model_file) as fh:
                 self.meshes = [Mesh.load_obj(line.strip(), self.device) for line in fh if line.strip()]
+
+    def render_python(self, width, height, parameters, im_syn, depth_syn, vertmap_syn, class_indexes, poses, centers,
+                      is_sampling, is_sampling_pose):
+        """`Synthesizer::render_python` (synthesize.cpp:323-342) with the reference's arguments: one sampled scene rendered
+        on the GPU (posecnn_amd.synthesize) into the caller's float32 arrays so that tools/train_net.py:176-258 binds
+        unchanged. parameters = (fx, fy, px, py, znear, zfar, tnear, tfar). im_syn [H,W,4]: BGRA in [0, 1] — (byte + 0.5) /
+        255, which the script's `np.clip(255 * im_syn, 0, 255).astype(np.uint8)` turns back into the rendered byte;
+        depth_syn [H,W,3]: the window depth whose conversion at :203-205 gives the rendered uint16 depth (factor 1000), 1
+        where nothing is hit; vertmap_syn [H,W,3]: object-frame point with x shifted by the 0-based class index, NaN
+        where nothing is hit; class_indexes [C] (0-based, -1 = unused), poses [C,7], centers [C,2] as the reference fills them.
+        With `model_file`, the models are read by `TexturedMesh.load_obj` (uvs + `map_Kd`, or vertex colours); `meshes`
+        passed directly are rendered with whatever colours / uvs / texture they carry, white without any. `pose_file` is
+        the reference's: a list of per-model pose files of 7-float rows (`Synthesizer::loadPoses`)."""
+        from . import synthesize as syn
+        if self.meshes is None:
+            self.setup(width, height)
+        fx, fy, px, py, znear, zfar, tnear, tfar = [float(x) for x in np.asarray(parameters).reshape(-1)[:8]]
+        K = np.array([[fx, 0, px], [0, fy, py], [0, 0, 1]], dtype=np.float64)
+        if self._bank is None:
+            # the lit render wants what `loadTexturedMesh` keeps (uvs + map_Kd image, or vertex colours); `Mesh.load_obj`
+            # reads positions, normals and faces only, which is all ICP needs, so the model files are read again here
+            models = self.meshes
+            if self.model_file:
+                with open(self.model_file) as fh:
+                    models = [syn.TexturedMesh.load_obj(line.strip()) for line in fh if line.strip()]
+            self._bank = syn.MeshBank(models, device=self.device)
+        key = (bool(is_sampling), bool(is_sampling_pose), tnear, tfar)
+        if self._sampler is None or self._sampler[0] != key:
+            table = syn.SceneSampler.load_pose_table(self.pose_file) if is_sampling_pose else None
+            self._sampler = (key, syn.SceneSampler(len(self.meshes), self.synthesis_seed, tnear, tfar, is_sampling, is_sampling_pose, table))
+        scene = self._sampler[1].sample()
+        batch = syn.render_scenes(self._bank, [scene], K, int(height), int(width), None, (znear, zfar), syn.FACTOR_DEPTH, 0)
+        color = batch.color[0].cpu().numpy()
+        depth = batch.depth[0].view(torch.int16).cpu().numpy().view(np.uint16)
+        label = batch.label[0].cpu().numpy()
+        hit = label > 0
+        im_syn[...] = np.where(hit[..., None], (color.astype(np.float64) + 0.5) / 255.0, 0.0)
+        z = (depth.astype(np.float64) + 0.5) / syn.FACTOR_DEPTH
+        window = (((zfar + znear) - 2.0 * zfar * znear / z) / (zfar - znear) + 1.0) / 2.0
+        depth_syn[...] = np.where(hit, window, 1.0)[..., None]
+        vm = batch.vertmap[0].cpu().numpy().copy()
+        vm[..., 0] += (label - 1)
+        vm[~hit] = np.nan
+        vertmap_syn[...] = vm
+        for i, (m, T, _) in enumerate(scene.instances):
+            class_indexes[i] = m
+            poses[i, :4] = mat2quat(T[:, :3])
+            poses[i, 4:7] = T[:, 3]
+            t = T[:, 3].astype(np.float32)
+            centers[m] = (np.float32(fx) * (t[0] / t[2]) + np.float32(px), np.float32(fy) * (t[1] / t[2]) + np.float32(py))
 
     def icp_python(self, labelmap, depth, parameters, height, width, num_roi, channel_roi, rois, poses, outputs, outputs_icp,
                    maxError, iterations=8, min_pixels=400, radius=0.01):

@@ -24,6 +24,15 @@ class TrainConfig(object):
     VERTEX_W = 5.0
     POSE_W = 1.0
     SNAPSHOT_ITERS = 10000
+    # online synthetic scenes (lib/fcn/config.py:74-88), read by posecnn_amd.synthesize.online_minibatches
+    SYNTHESIZE = False
+    SYN_ONLINE = False
+    SYN_WIDTH = 640
+    SYN_HEIGHT = 480
+    SYN_TNEAR = 0.5
+    SYN_TFAR = 2.0
+    SYN_SAMPLE_OBJECT = True
+    SYN_SAMPLE_POSE = False
 
 
 def loss_cross_entropy_single_frame(scores, labels):
