@@ -14,7 +14,9 @@
 // v_mfma_f32_16x16x4_f32 (exact f32), global -> LDS DMA into a 2-stage ring (64 KB: TWO workgroups per
 // CU, which like the trunk's pairs drift out of phase and cover each other's barrier and DMA waits —
 // fc6 at 468 rows 1.38 -> 1.15 ms against the 3-stage ring with one workgroup per CU) with XOR-swizzled
-// 16-byte chunks, one barrier per 64-deep K stage, K loop software pipelined by half a stage, epilogue
+// 16-byte chunks, one barrier per 64-deep K stage, K loop software pipelined by half a stage (the ring
+// position travels in the offset field of the ds_read_b128s, two copies of the reads behind a scalar
+// branch: a stage has no vector-ALU instruction between its 32 MFMAs), epilogue
 // through LDS for 256-byte row stores, XCD-aware block map (the column blocks that share a row block's x
 // rows run on one XCD). `wt` is the weight matrix TRANSPOSED ([N][K], K contiguous) so that both operands
 // are K-major rows for the DMA.
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   // ldy / nvalid (pcnn_fc_rows_cols_fwd): y has `ldy` floats per row and only output columns < nvalid exist (the weight rows
   // past them are zero padding up to the kernel's 64-column blocks); y2, if given, receives tanh(y). Plain fc_rows: ldy =
   // nvalid = N, y2 = NULL.
-  __shared__ __attribute__((aligned(16))) float smem[FC_NBUF * 128 * FC_LD];   // sA[3][64][64] | sB[3][64][64]
+  __shared__ __attribute__((aligned(16))) float smem[FC_NBUF * 128 * FC_LD];   // sA[2][64][64] | sB[2][64][64]; epilogue: [64][64]
   float* sAp = smem;
   float* sBp = smem + FC_NBUF * 64 * FC_LD;
 
@@ -168,14 +170,26 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   v4f xa0[2], xa1[2], xb[2], ya0[2], ya1[2], yb[2];
 #pragma unroll
   for (int g = 0; g < 2; g++) xa0[g] = xa1[g] = xb[g] = ya0[g] = ya1[g] = yb[g] = (v4f){0.f, 0.f, 0.f, 0.f};
-#define FC_DSREAD(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(DST) : "v"(ADDR))
-#define FC_READ(SA0, SA1, SB, G0)                                             \
+  // The ring position is part of the INSTRUCTION: buffer `cur` of either operand starts cur * 16384 bytes behind buffer 0 (second
+  // row block + 4096), which goes into ds_read_b128's offset field — the lane's 8 chunk addresses adA / adB are loop invariants
+  // and a stage reads with no vector arithmetic (csrc/wino_mfma.hip, WM_READ: a v_add_u32 next to MFMAs is never hidden; here
+  // the adds also wrote registers an MFMA had just read, behind 3- and 8-cycle s_nops). The six reads of a half stage exist
+  // once per buffer; `cur` (wave-uniform, on the scalar unit) picks the copy with a scalar branch.
+  // Built and dropped: the stage loop unrolled over the two buffers (no branch; the second stage skipped at the end of an odd
+  // split). Same registers, same K loop ISA per stage, and fc6 gained the same 4-5 %, but launches of ONE round of workgroups
+  // lost: fc7's shape at 512 live rows 0.182 -> 0.193 ms (best case 0.145 -> 0.187), at 684 rows 0.213 -> 0.240, where the
+  // form below gives 0.183 and 0.209 (200 launches each, parent / unrolled / branch alternating on one GPU).
+#define FC_DSREAD(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "i"(OFF))
+#define FC_READ_AT(SA0, SA1, SB, G0, CUR)                                     \
   _Pragma("unroll") for (int g_ = 0; g_ < 2; g_++) {                          \
-    const unsigned aa_ = adA[(G0) + g_] + curo, ab_ = adB[(G0) + g_] + curo;  \
-    FC_DSREAD(SB[g_], ab_, 0);                                                \
-    FC_DSREAD(SA0[g_], aa_, 0);                                               \
-    FC_DSREAD(SA1[g_], aa_, 4096);                                            \
+    FC_DSREAD(SB[g_], adB[(G0) + g_], (CUR) * (64 * FC_LD * 4));              \
+    FC_DSREAD(SA0[g_], adA[(G0) + g_], (CUR) * (64 * FC_LD * 4));             \
+    FC_DSREAD(SA1[g_], adA[(G0) + g_], (CUR) * (64 * FC_LD * 4) + 4096);      \
   }
+#define FC_READ(SA0, SA1, SB, G0)                                             \
+  if (cur == 0) { FC_READ_AT(SA0, SA1, SB, G0, 0); }                          \
+  else { FC_READ_AT(SA0, SA1, SB, G0, 1); }
+  static_assert(FC_NBUF == 2, "FC_READ dispatches over a ring of two buffers");
 #define FC_MFMA1(SA0, SA1, SB, G)                                                             \
   _Pragma("unroll") for (int i_ = 0; i_ < 4; i_++) {                                          \
     acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(SA0[G][i_], SB[G][i_], acc0, 0, 0, 0);        \
@@ -187,7 +201,6 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   for (int s = 0; s < NK; s++) {
     if (FC_NBUF == 3) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    const unsigned curo = (unsigned)cur * (64 * FC_LD * 4);
     FC_READ(xa0, xa1, xb, 0);
     __builtin_amdgcn_sched_barrier(0);
     FC_MFMA1(ya0, ya1, yb, 0) FC_MFMA1(ya0, ya1, yb, 1)
@@ -220,6 +233,7 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   __syncthreads();   // ... and every LDS read is done: the buffers can be recycled
 #undef FC_DMA
 #undef FC_READ
+#undef FC_READ_AT
 #undef FC_DSREAD
 #undef FC_MFMA1
 

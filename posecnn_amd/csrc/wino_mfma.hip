@@ -30,7 +30,10 @@
 //    lane-linear one (rows of 64 floats, unpadded); bank conflicts are avoided by an XOR swizzle of
 //    the 16-byte chunk index with the row (applied to the SOURCE address of the DMA and to the
 //    ds_read_b128 address — the same involution on both sides). One b128 read feeds 4 MFMAs (K is
-//    consumed in the order 16 j + 4 (lane >> 4) + i for both operands).
+//    consumed in the order 16 j + 4 (lane >> 4) + i for both operands). A lane's 8 read addresses are
+//    loop invariants: the ring position travels in the reads' offset field (three copies of a half
+//    stage's six reads behind a scalar branch), so a stage has NO vector-ALU instruction between its
+//    32 MFMAs — on gfx950 a VALU instruction is never hidden behind an MFMA of its SIMD.
 //  * Epilogue: bias + ReLU (+ 2x2 max-pool of the 4x4 tile) in registers, then through LDS (two staging
 //    buffers, one barrier per pass) so that every store instruction writes whole 256-byte channel rows
 //    (the C/D layout alone would give 64-byte segments).
@@ -252,15 +255,35 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     adA[j] = lds0 + (unsigned)ra0 * 4u + chb;
     adB[j] = lds0 + (unsigned)(WM_NBUF * BT * WM_LD + rb) * 4u + chb;
   }
+// The ring position is part of the INSTRUCTION, not of the address (WR == 1): buffer `cur` of the A operand starts
+// cur * 8192 bytes behind buffer 0 (second row block + 4096), of the B operand cur * 16384 — at most 32 768, inside
+// ds_read_b128's 16-bit offset field — so the lane's 8 chunk addresses adA / adB are loop invariants and a stage
+// reads with no vector arithmetic at all (the 8 v_add_u32 per stage of rounds 2-6 each cost ~3.5 cycles of matrix
+// time: a VALU instruction never hides behind an MFMA of its SIMD). The six reads of a half stage exist once per ring
+// position and `cur` (wave-uniform, on the scalar unit) picks the copy with a scalar branch; everything else of the stage
+// exists once. WR == 2 (64 KB of ring: the sums pass 65 535) keeps the add, and so does the ablation without LDS reads.
 #define WM_DSREAD(DST, ADDR, OFF)                                                                     \
-  if constexpr (!(ABL & 4)) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(DST) : "v"(ADDR)); \
+  if constexpr (!(ABL & 4)) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "i"(OFF)); \
   else asm volatile("" : "+v"(DST) : "v"(ADDR))
-#define WM_READ(SA0, SA1, SB, G0)                                                                     \
+#define WM_READ_AT(SA0, SA1, SB, G0, CUR)                                                             \
   _Pragma("unroll") for (int g_ = 0; g_ < 2; g_++) {                                                  \
-    const unsigned aa_ = adA[(G0) + g_] + curA, ab_ = adB[(G0) + g_] + curB;                           \
-    WM_DSREAD(SB[g_], ab_, 0);                                                                        \
-    WM_DSREAD(SA0[g_], aa_, 0);                                                                       \
-    WM_DSREAD(SA1[g_], aa_, 4096);   /* 16 rows further */                                             \
+    WM_DSREAD(SB[g_], adB[(G0) + g_], (CUR) * (64 * WM_LD * 4));                                      \
+    WM_DSREAD(SA0[g_], adA[(G0) + g_], (CUR) * (BT * WM_LD * 4));                                     \
+    WM_DSREAD(SA1[g_], adA[(G0) + g_], (CUR) * (BT * WM_LD * 4) + 4096);   /* 16 rows further */       \
+  }
+#define WM_READ(SA0, SA1, SB, G0)                                                                     \
+  if constexpr (WR == 1 && !(ABL & 4)) {                                                              \
+    if (cur == 0) { WM_READ_AT(SA0, SA1, SB, G0, 0); }                                                \
+    else if (cur == 1) { WM_READ_AT(SA0, SA1, SB, G0, 1); }                                           \
+    else { WM_READ_AT(SA0, SA1, SB, G0, 2); }                                                         \
+  } else {                                                                                            \
+    const unsigned curA = (unsigned)cur * (BT * WM_LD * 4), curB = (unsigned)cur * (64 * WM_LD * 4);  \
+    _Pragma("unroll") for (int g_ = 0; g_ < 2; g_++) {                                                \
+      const unsigned aa_ = adA[(G0) + g_] + curA, ab_ = adB[(G0) + g_] + curB;                         \
+      WM_DSREAD(SB[g_], ab_, 0);                                                                      \
+      WM_DSREAD(SA0[g_], aa_, 0);                                                                     \
+      WM_DSREAD(SA1[g_], aa_, 4096);   /* 16 rows further */                                           \
+    }                                                                                                 \
   }
 #define WM_MFMA1(SA0, SA1, SB, G, ACC)                                                                \
   if constexpr (ABL & 8) { asm volatile("" :: "v"(SA0[G]), "v"(SA1[G]), "v"(SB[G])); } else           \
@@ -329,12 +352,11 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     if constexpr (ABL & 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                 \
     else if constexpr (UB == 2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
     else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");                     \
-    const unsigned curA = (unsigned)cur * (BT * WM_LD * 4), curB = (unsigned)cur * (64 * WM_LD * 4);      \
     WM_READ(xa0, xa1, xb, 0);                                                                         \
     __builtin_amdgcn_sched_barrier(0);   /* the X reads go out first: their latency hides under Y's MFMAs */ \
     if (kc > 0) { WM_MFMA(ya0, ya1, yb, acc[XI]); }                                                   \
     else if ((XI) > 0) { WM_MFMA(ya0, ya1, yb, acc[XP]); }                                            \
-    else if (nu > 0) { WM_MFMA(ya0, ya1, yb, acc[5]); WM_FOLD(nu - 1); }                              \
+    else if (nu > 0) { WM_MFMA(ya0, ya1, yb, acc[5]); WM_FOLD(nup); }                                 \
     {                                                                                                 \
       const int nb = cur >= 1 ? cur - 1 : 2;   /* (cur + 2) % 3: the previous stage's buffer */         \
       WM_DMA(nb, pvo, puo);                                                                           \
@@ -353,7 +375,11 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   /* Y landed before the compiler may touch its registers (loop-carried) */ \
     cur = cur == 2 ? 0 : cur + 1;                                                                     \
   } while (0)
+  static_assert(WM_NBUF == 3, "WM_READ dispatches over a ring of three buffers");
 
+  // nu - 1 as a scalar loop variable of its own: written `nu - 1` next to the `nu > 0` test the compiler fuses the two into one
+  // VECTOR subtract-with-borrow, whose result now outlives the X reads of the stage (one VGPR more than the kernel had)
+  int nup = -1;
   for (int nu = 0; nu < 6; nu++) {
     for (int kc = 0; kc < NK; kc++) WM_STAGE(0, 5);
     for (int kc = 0; kc < NK; kc++) WM_STAGE(1, 0);
@@ -361,6 +387,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     for (int kc = 0; kc < NK; kc++) WM_STAGE(3, 2);
     for (int kc = 0; kc < NK; kc++) WM_STAGE(4, 3);
     for (int kc = 0; kc < NK; kc++) WM_STAGE(5, 4);
+    nup = nu;
   }
   // drain: K groups 2, 3 of the last stage, the last column, and every LDS read before the buffers
   // are recycled for the epilogue
@@ -375,6 +402,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
   __syncthreads();
 #undef WM_STAGE
 #undef WM_READ
+#undef WM_READ_AT
 #undef WM_DSREAD
 #undef WM_MFMA
 #undef WM_MFMA1
