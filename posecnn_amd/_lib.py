@@ -1,5 +1,5 @@
 """ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h, include/posecnn_hip_train.h,
-include/posecnn_hip_frontend.h and include/posecnn_hip_synth.h).
+include/posecnn_hip_frontend.h, include/posecnn_hip_synth.h and include/posecnn_hip_augment.h).
 
 This is the Python-side analogue of the reference's ``tf.load_op_library('<op>.so')`` stubs
 (lib/hough_voting_gpu_layer/hough_voting_gpu_op.py:4-7 and siblings). The library is built
@@ -8,7 +8,7 @@ if the shared object is missing or an entry point fails, the call raises.
 """
 import ctypes
 import os
-from ctypes import (POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p)
+from ctypes import (POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libposecnn_hip.so")
@@ -138,6 +138,12 @@ SYNTH_SIGNATURES = {
                                      _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# the training-augmentation entries of include/posecnn_hip_augment.h (same library, same ABI version)
+AUGMENT_SIGNATURES = {
+    "pcnn_augment_frames_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "pcnn_augment_frames_fwd": (c_int, [_P, c_int, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+}
+
 
 def profile_enable(on=True):
     """Bracket every library kernel launch with HIP events on its launch stream."""
@@ -184,7 +190,7 @@ def lib():
         import torch  # noqa: F401
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) +\
-                list(SYNTH_SIGNATURES.items()):
+                list(SYNTH_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args

@@ -23,7 +23,7 @@ __all__ = [
     "average_distance_loss", "backproject", "softmax_argmax", "deconv_bilinear", "bias_act_",
     "hough_voting_grad", "hard_label_grad", "hough_rows_capacity",
     "upscore_softmax_argmax", "Workspace", "vertex_targets", "smooth_l1_loss_vertex_gt",
-    "depth_normals", "bilateral_filter_u8", "normal_image", "bilateral_tables",
+    "depth_normals", "bilateral_filter_u8", "normal_image", "bilateral_tables", "augment_frames",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1240,3 +1240,55 @@ def normal_image(depth, intrinsics, factor_depth=None, depth_cutoff=20.0, d=9, s
           lib().pcnn_normal_image_fwd(_ptr(f32), _ptr(u16), factor, _ptr(intr), B, H, W, float(depth_cutoff), int(d),
                                       _ptr(color), _ptr(space), taps, _ptr(out), _stream(out)))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# training augmentation (include/posecnn_hip_augment.h): chromatic_transform + add_noise + the blob, one kernel
+AUGMENT_ROW = 10
+DEPTH_NORMS = {"frame_max": 0, "fixed_2000": 1}
+
+
+def augment_frames(color, depth=None, params=None, seed=0, pixel_means=None, depth_norm="frame_max"):
+    """`chromatic_transform` and `add_noise` (lib/utils/blob.py:74-129) in the order of
+    lib/gt_synthesize_layer/minibatch.py:170-201, fused with the blob formation: color uint8 [B,H,W,3] BGR or [B,H,W,4]
+    BGRA (the fourth byte is ignored: `SceneBatch.color` goes in as it is), depth uint16 [B,H,W] or None.
+    params: host float64 [B,10], one row per frame (`augment.AugmentSampler.sample`; columns and arithmetic:
+    include/posecnn_hip_augment.h). seed: an integer below 2^128, the Philox key. depth_norm: "frame_max" (the frame's own
+    maximum, minibatch.py:189) or "fixed_2000" (clip(d / 2000, 0, 1) 255, what `networks.raw_frame_blob` forms).
+    Returns (data, data_p): f32 [B,H,W,3] blobs with PIXEL_MEANS subtracted; data_p is None without depth."""
+    from .config import PIXEL_MEANS
+    color = _dev(color, "color", torch.uint8)
+    if color.dim() != 4 or color.shape[3] not in (3, 4):
+        raise ValueError("color must be uint8 [B,H,W,3] or [B,H,W,4] (got %s)" % (tuple(color.shape),))
+    B, H, W, C = color.shape
+    if depth is not None:
+        depth = _dev(depth, "depth", torch.uint16)
+        if depth.dim() == 4 and depth.shape[3] == 1:
+            depth = depth.reshape(depth.shape[:3])
+        if tuple(depth.shape) != (B, H, W):
+            raise ValueError("depth must be uint16 [%d,%d,%d] (got %s)" % (B, H, W, tuple(depth.shape)))
+    if depth_norm not in DEPTH_NORMS:
+        raise ValueError("depth_norm must be one of %s (got %r)" % (sorted(DEPTH_NORMS), depth_norm))
+    if params is None:
+        raise ValueError("augment_frames needs params: one row of %d doubles per frame" % AUGMENT_ROW)
+    rows = np.ascontiguousarray(params, dtype=np.float64)
+    if rows.shape != (B, AUGMENT_ROW):
+        raise ValueError("params must be [%d,%d] (got %s)" % (B, AUGMENT_ROW, rows.shape))
+    seed = int(seed)
+    if not 0 <= seed < 1 << 128:
+        raise ValueError("seed must be in [0, 2^128)")
+    means = (ctypes.c_double * 3)(*[float(m) for m in np.asarray(PIXEL_MEANS if pixel_means is None else pixel_means, dtype=np.float64).reshape(-1)[:3]])
+    color, depth = _aligned16(color), (_aligned16(depth) if depth is not None else None)
+    dev = color.device
+    data = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    data_p = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if depth is not None else None
+    norm = DEPTH_NORMS[depth_norm]
+    nbytes = c_size_t()
+    check("pcnn_augment_frames_workspace_bytes",
+          lib().pcnn_augment_frames_workspace_bytes(B, 1 if depth is not None else 0, norm, ctypes.byref(nbytes)))
+    ws = _ws(dev, "augment_frames").get(nbytes.value, dev) if nbytes.value else None
+    check("pcnn_augment_frames_fwd",
+          lib().pcnn_augment_frames_fwd(_ptr(color), C, _ptr(depth), ctypes.c_void_p(rows.ctypes.data), means,
+                                        seed & (1 << 64) - 1, seed >> 64, norm, B, H, W, _ptr(data), _ptr(data_p), _ptr(ws),
+                                        nbytes.value, _stream(data)))
+    return data, data_p

@@ -9,7 +9,10 @@ background paste of lib/gt_synthesize_layer/minibatch.py:113-154 — as one libr
     for feed, batch in synthetic_minibatches(...): solver.train_step(feed)
 
 The kernel's arithmetic (posecnn_amd/csrc/synth_scene.hip) is this library's own: GL's rasteriser, texture filter and `pow`
-have no reproducible bits. `chromatic_transform`, `add_noise` and the random flip of minibatch.py:170-178 are not here.
+have no reproducible bits. `chromatic_transform` and `add_noise` of minibatch.py:170-175 run on the device as well
+(`feed(..., augment=AugmentSampler(...))`, posecnn_amd/augment.py, one `ops.augment_frames` call). Only the random flip of
+minibatch.py:177-178 is absent: the followed configuration, experiments/cfgs/lov_color_2d.yml:19-21, sets USE_FLIPPED: False,
+so the reference never trains on a flipped frame.
 """
 import ctypes
 import math
@@ -385,20 +388,28 @@ class SceneBatch:
                 self.scenes[i] = other.scenes[k]
         self.pixel_counts = torch.cat(parts) if parts else self.pixel_counts
 
-    def feed(self, extents, points, symmetry, rgbd=False, keep_prob=1.0, w_inside=10.0):
+    def feed(self, extents, points, symmetry, rgbd=False, keep_prob=1.0, w_inside=10.0, augment=None):
         """The training feed without a download: `gt_label_2d` is the label tensor itself, `data` the BGR bytes of the
         colour frame (a raw uint8 frame: the first-layers kernel forms the blob), `data_p` the uint16 depth frame in the
-        RGB-D mode; the object table, the pose rows and the camera rows are built on the host and uploaded."""
+        RGB-D mode; the object table, the pose rows and the camera rows are built on the host and uploaded.
+        augment: an `augment.AugmentSampler`; `data` (and `data_p`) are then the f32 blobs of `ops.augment_frames` on the
+        BGRA frame as it is (minibatch.py:170-201: chromatic, noise, minus PIXEL_MEANS; depth over its own maximum), drawn
+        with the rows kept in `self.augment_rows`."""
         if self.height % 16 or self.width % 16:
             raise ValueError("SceneBatch.feed: render at a height and width that are multiples of 16 (got %dx%d)" % (self.height, self.width))
         dev = self.label.device
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
         tabs = self.tables(w_inside)
-        feed = {"data": self.color[..., :3].contiguous(), "gt_label_2d": self.label, "keep_prob": keep_prob,
+        if augment is None:
+            data, data_p = self.color[..., :3].contiguous(), self.depth
+        else:
+            self.augment_rows = augment.sample(len(self.scenes))
+            data, data_p = ops.augment_frames(self.color, self.depth if rgbd else None, self.augment_rows, augment.seed)
+        feed = {"data": data, "gt_label_2d": self.label, "keep_prob": keep_prob,
                 "vertex_objects": t(tabs["vertex_objects"]), "poses": t(tabs["poses"]), "meta_data": t(tabs["meta_data"]),
                 "extents": t(extents), "points": t(points), "symmetry": t(symmetry)}
         if rgbd:
-            feed["data_p"] = self.depth
+            feed["data_p"] = data_p
         return feed
 
 
@@ -447,13 +458,14 @@ def render_scenes(bank, scenes, K, height, width, background=None, depth_range=(
 
 
 def synthetic_minibatches(bank, sampler, K, height, width, batch_size, extents, points, symmetry, backgrounds=None, rgbd=False,
-                          min_pixels=MIN_PIXELS, depth_range=(Z_NEAR, Z_FAR), factor_depth=FACTOR_DEPTH, max_redraws=100):
+                          min_pixels=MIN_PIXELS, depth_range=(Z_NEAR, Z_FAR), factor_depth=FACTOR_DEPTH, max_redraws=100,
+                          augment=None):
     """The SYN_ONLINE data path: yields (feed, batch) forever. A scene whose `valid` flag is 0 — an object owns fewer
     than `min_pixels` label pixels — is drawn again, the reference's `continue` (train_net.py:220-228). Cost: one
     read of the `valid` flags per render call (the only host synchronisation of the feed), and only the re-drawn
     scenes are rendered again, over their own backgrounds; their frames replace the invalid ones inside the batch's
     tensors. backgrounds: callable(batch_size) -> uint8 [B,H,W,3] BGR device tensor, or None. `batch.redraws` counts the
-    scenes that were drawn again."""
+    scenes that were drawn again. augment: an `augment.AugmentSampler` for `SceneBatch.feed`, or None (clean renders)."""
     while True:
         scenes = [sampler.sample() for _ in range(batch_size)]
         bg = backgrounds(batch_size) if backgrounds is not None else None
@@ -471,14 +483,18 @@ def synthetic_minibatches(bank, sampler, K, height, width, batch_size, extents, 
             batch.redraws += len(bad)
         else:
             raise RuntimeError("synthetic_minibatches: no valid batch after %d draws (min_pixels = %d)" % (max_redraws, min_pixels))
-        yield batch.feed(extents, points, symmetry, rgbd=rgbd), batch
+        yield batch.feed(extents, points, symmetry, rgbd=rgbd, augment=augment), batch
 
 
-def online_minibatches(cfg, bank, K, batch_size, extents, points, symmetry, seed=0, pose_table=None, **kw):
+def online_minibatches(cfg, bank, K, batch_size, extents, points, symmetry, seed=0, pose_table=None, augment_seed=None, **kw):
     """How a trainer selects the path: the reference's switches, `cfg.SYNTHESIZE and cfg.SYN_ONLINE`
     (tools/train_net.py:302), and its `cfg.SYN_*` settings (lib/fcn/config.py:74-88; `train.TrainConfig` carries them)
-    -> `synthetic_minibatches` at cfg.SYN_HEIGHT x cfg.SYN_WIDTH. Raises when the switches are off."""
+    -> `synthetic_minibatches` at cfg.SYN_HEIGHT x cfg.SYN_WIDTH. Raises when the switches are off. augment_seed: when given,
+    the frames are augmented by `AugmentSampler(augment_seed, cfg.CHROMATIC, cfg.ADD_NOISE)` (lib/fcn/config.py:112-113)."""
     if not (getattr(cfg, "SYNTHESIZE", False) and getattr(cfg, "SYN_ONLINE", False)):
         raise ValueError("online_minibatches: cfg.SYNTHESIZE and cfg.SYN_ONLINE are not both set")
     sampler = SceneSampler(len(bank), seed, cfg.SYN_TNEAR, cfg.SYN_TFAR, cfg.SYN_SAMPLE_OBJECT, cfg.SYN_SAMPLE_POSE, pose_table)
+    if augment_seed is not None:
+        from .augment import AugmentSampler
+        kw["augment"] = AugmentSampler(augment_seed, getattr(cfg, "CHROMATIC", True), getattr(cfg, "ADD_NOISE", False))
     return synthetic_minibatches(bank, sampler, K, cfg.SYN_HEIGHT, cfg.SYN_WIDTH, batch_size, extents, points, symmetry, **kw)

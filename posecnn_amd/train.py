@@ -33,6 +33,9 @@ class TrainConfig(object):
     SYN_TFAR = 2.0
     SYN_SAMPLE_OBJECT = True
     SYN_SAMPLE_POSE = False
+    # data augmentation (lib/fcn/config.py:112-113), read by online_minibatches when it is given an augment_seed
+    CHROMATIC = True
+    ADD_NOISE = False
 
 
 def loss_cross_entropy_single_frame(scores, labels):
