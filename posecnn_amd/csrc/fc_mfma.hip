@@ -10,7 +10,7 @@
 //
 //   y[m, n] = [ReLU](sum_k x[m, k] wt[n, k] + bias[n])   m < min(M_cap, *num_rows_dev), else 0
 //
-// Same machinery as csrc/wino_mfma.hip, minus the Winograd planes: 64 x 64 block per 8-wave workgroup,
+// Same machinery as csrc/wino_mfma.hip (csrc/mfma_ring.h), minus the Winograd planes: 64 x 64 block per 8-wave workgroup,
 // v_mfma_f32_16x16x4_f32 (exact f32), global -> LDS DMA into a 2-stage ring (64 KB: TWO workgroups per
 // CU, which like the trunk's pairs drift out of phase and cover each other's barrier and DMA waits —
 // fc6 at 468 rows 1.38 -> 1.15 ms against the 3-stage ring with one workgroup per CU) with XOR-swizzled
@@ -23,23 +23,14 @@
 #include <algorithm>
 
 #include "pcnn_device.h"
+#include "mfma_ring.h"
 
 namespace {
 
 using namespace pcnn;
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int FC_LD = 64;
-constexpr int FC_NBUF = 2;
-
-// 16 bytes per lane, global -> LDS: SGPR base + 32-bit VGPR byte offset, LDS base in M0 (spelled out in asm
-// like wino_mfma.hip's glds16_s: through the builtin the compiler builds 64-bit VGPR addresses per load).
-__device__ __forceinline__ void fc_glds16_s(const char* sbase, unsigned voff, unsigned lds_addr)
-{
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(lds_addr) : "memory", "m0");
-}
+constexpr int FC_NBUF = 2;    // stage buffers in the LDS ring (prefetch distance 1)
 
 // Split-K factor, decided ON THE DEVICE from the live row count (same value in every workgroup of the
 // launch and in the reduction kernel): with few live rows there are few (row block, column block)
@@ -87,8 +78,6 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   // past them are zero padding up to the kernel's 64-column blocks); y2, if given, receives tanh(y). Plain fc_rows: ldy =
   // nvalid = N, y2 = NULL.
   __shared__ __attribute__((aligned(16))) float smem[FC_NBUF * 128 * FC_LD];   // sA[2][64][64] | sB[2][64][64]; epilogue: [64][64]
-  float* sAp = smem;
-  float* sBp = smem + FC_NBUF * 64 * FC_LD;
 
   // XCD-aware block map: the weight matrix is the big operand (fc6: 411 MB) and every row block needs
   // all of a column block's rows of it, so XCD x takes the column blocks cb == x (mod 8) and runs their
@@ -128,10 +117,10 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
 
   const int dr0 = 8 * wave + lk, dr1 = dr0 + 4;
   const int ra_ = min(m0 + dr0, mlast), rb_ = min(m0 + dr1, mlast);   // rows past the count: any finite data, zeroed at the end
-  const unsigned va0 = (unsigned)(((size_t)ra_ * K + (lr ^ (dr0 & 15)) * 4) * 4);
-  const unsigned va1 = (unsigned)(((size_t)rb_ * K + (lr ^ (dr1 & 15)) * 4) * 4);
-  const unsigned ub0 = (unsigned)(((size_t)(cb * 64 + dr0) * K + (lr ^ (dr0 & 15)) * 4) * 4);
-  const unsigned ub1 = (unsigned)(((size_t)(cb * 64 + dr1) * K + (lr ^ (dr1 & 15)) * 4) * 4);
+  const unsigned va0 = (unsigned)(((size_t)ra_ * K + ring_src_col(lr, dr0)) * 4);
+  const unsigned va1 = (unsigned)(((size_t)rb_ * K + ring_src_col(lr, dr1)) * 4);
+  const unsigned ub0 = (unsigned)(((size_t)(cb * 64 + dr0) * K + ring_src_col(lr, dr0)) * 4);
+  const unsigned ub1 = (unsigned)(((size_t)(cb * 64 + dr1) * K + ring_src_col(lr, dr1)) * 4);
   const char* xbase = reinterpret_cast<const char*>(x);
   const char* wbase = reinterpret_cast<const char*>(wt);
   const int ldsw = 8 * wave * FC_LD;
@@ -145,17 +134,16 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
     const char* ws_ = wbase + (size_t)(KO) * 4;                                          \
     const unsigned la_ = lds_a0 + (unsigned)(BUF) * (64 * FC_LD * 4);                    \
     const unsigned lb_ = lds_b0 + (unsigned)(BUF) * (64 * FC_LD * 4);                    \
-    fc_glds16_s(xs_, va0, la_);                                                          \
-    fc_glds16_s(xs_, va1, la_ + 4 * FC_LD * 4);                                          \
-    fc_glds16_s(ws_, ub0, lb_);                                                          \
-    fc_glds16_s(ws_, ub1, lb_ + 4 * FC_LD * 4);                                          \
+    glds16_s(xs_, va0, la_);                                                          \
+    glds16_s(xs_, va1, la_ + 4 * FC_LD * 4);                                          \
+    glds16_s(ws_, ub0, lb_);                                                          \
+    glds16_s(ws_, ub1, lb_ + 4 * FC_LD * 4);                                          \
   } while (0)
 
   v4f acc0 = (v4f){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
   int pk = kfirst * 64;   // K offset (floats) of the prefetch pointer; parks on the split's last stage
   const int kpark = klast * 64 - 64;
-  FC_DMA(0, pk); pk = min(pk + 64, kpark);
-  if (FC_NBUF == 3) { FC_DMA(1, pk); pk = min(pk + 64, kpark); }
+  FC_DMA(0, pk); pk = min(pk + 64, kpark);   // prologue: stage 0 in flight
   int cur = 0;
 
   const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)smem;
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   unsigned adA[4], adB[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    const unsigned chb = (unsigned)(((4 * j + lk) ^ lr) * 16);
+    const unsigned chb = ring_chunk_bytes(j, lk, lr);
     adA[j] = lds0 + (unsigned)ra0 * 4u + chb;
     adB[j] = lds0 + (unsigned)(FC_NBUF * 64 * FC_LD + rb) * 4u + chb;
   }
@@ -179,12 +167,11 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   // split). Same registers, same K loop ISA per stage, and fc6 gained the same 4-5 %, but launches of ONE round of workgroups
   // lost: fc7's shape at 512 live rows 0.182 -> 0.193 ms (best case 0.145 -> 0.187), at 684 rows 0.213 -> 0.240, where the
   // form below gives 0.183 and 0.209 (200 launches each, parent / unrolled / branch alternating on one GPU).
-#define FC_DSREAD(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "i"(OFF))
 #define FC_READ_AT(SA0, SA1, SB, G0, CUR)                                     \
   _Pragma("unroll") for (int g_ = 0; g_ < 2; g_++) {                          \
-    FC_DSREAD(SB[g_], adB[(G0) + g_], (CUR) * (64 * FC_LD * 4));              \
-    FC_DSREAD(SA0[g_], adA[(G0) + g_], (CUR) * (64 * FC_LD * 4));             \
-    FC_DSREAD(SA1[g_], adA[(G0) + g_], (CUR) * (64 * FC_LD * 4) + 4096);      \
+    RING_DSREAD_B128(SB[g_], adB[(G0) + g_], (CUR) * (64 * FC_LD * 4));              \
+    RING_DSREAD_B128(SA0[g_], adA[(G0) + g_], (CUR) * (64 * FC_LD * 4));             \
+    RING_DSREAD_B128(SA1[g_], adA[(G0) + g_], (CUR) * (64 * FC_LD * 4) + 4096);      \
   }
 #define FC_READ(SA0, SA1, SB, G0)                                             \
   if (cur == 0) { FC_READ_AT(SA0, SA1, SB, G0, 0); }                          \
@@ -199,13 +186,12 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
   // stage s: own DMAs landed (the next stage's stay in flight) -> barrier -> reads X(s) -> MFMAs Y(s-1)
   // + DMA of stage s+2 -> X landed -> MFMAs X(s), reads Y(s) in between. Y of "stage -1" is zeros.
   for (int s = 0; s < NK; s++) {
-    if (FC_NBUF == 3) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (two buffers: nothing else is in flight)
     FC_READ(xa0, xa1, xb, 0);
     __builtin_amdgcn_sched_barrier(0);
     FC_MFMA1(ya0, ya1, yb, 0) FC_MFMA1(ya0, ya1, yb, 1)
     {
-      const int nb = FC_NBUF == 3 ? (cur >= 1 ? cur - 1 : 2) : (cur ^ 1);
+      const int nb = cur ^ 1;   // the buffer the previous stage just freed
       FC_DMA(nb, pk);
       pk = min(pk + 64, kpark);
     }
@@ -219,7 +205,7 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
     FC_MFMA1(xa0, xa1, xb, 1)
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    cur = FC_NBUF == 3 ? (cur == 2 ? 0 : cur + 1) : (cur ^ 1);
+    cur = cur ^ 1;
   }
   __builtin_amdgcn_sched_barrier(0);
   FC_MFMA1(ya0, ya1, yb, 0) FC_MFMA1(ya0, ya1, yb, 1)
@@ -234,7 +220,6 @@ __global__ __launch_bounds__(512, 4) void fc_rows_mfma_kernel(
 #undef FC_DMA
 #undef FC_READ
 #undef FC_READ_AT
-#undef FC_DSREAD
 #undef FC_MFMA1
 
   // epilogue: lane holds rows 32 wm + 16 b + 4 lk + i (b = 0: acc0, 1: acc1) x column 16 wn + lr
@@ -317,6 +302,36 @@ bool fc_can_split(int rows_capacity, int in_features, int out_features)
   return rows_capacity <= out_features && in_features >= 1024;   // not the tall (1x1 conv) shape; a K worth splitting
 }
 
+// The host path of the three entries below: the shared argument checks in their fixed order (`who` is the entry's name in
+// every message), the block map and the launch of fc_rows_mfma_kernel with N output columns. What is an entry's own comes
+// in from it: `own_checks` (its width / activation rules, which report between the shape checks and the empty-buffer
+// return), `given` / `aligned` over ITS pointers with `names` their list in the message, and the kernel's routing arguments.
+// *launched stays false when the call returned before the launch (an error, or rows_capacity == 0: nothing to do).
+template <class OwnChecks>
+int fc_rows_launch(const char* who, OwnChecks own_checks, bool given, bool aligned, const char* names, bool* launched,
+                   const float* x, const float* wt, const float* bias, const float* addend, float* y, int rows_capacity,
+                   int in_features, int N, int relu, const int32_t* num_rows_dev, float* part, int smax, int wscap, int ldy,
+                   int nvalid, float* y2, int split_col, float* y_b, int relu_b, hipStream_t stream)
+{
+  *launched = false;
+  PCNN_REQUIRE(rows_capacity >= 0, PCNN_EINVAL, "%s: negative row capacity", who);
+  PCNN_REQUIRE(in_features >= 128 && in_features % 64 == 0, PCNN_EINVAL,
+               "%s: in_features must be a multiple of 64, >= 128 (got %d)", who, in_features);
+  if (const int st = own_checks()) return st;
+  if (rows_capacity == 0) return PCNN_OK;
+  PCNN_REQUIRE(given, PCNN_ENULL, "%s: NULL pointer", who);
+  PCNN_REQUIRE(aligned, PCNN_EINVAL, "%s: pointers (%s) must be 16-byte aligned", who, names);
+  PCNN_REQUIRE((long long)rows_capacity * in_features < (1ll << 30) && (long long)N * in_features < (1ll << 30),
+               PCNN_EINVAL, "%s: operand larger than the 32-bit byte offsets of the kernel", who);
+  const int nbm = (rows_capacity + 63) / 64, ncb = N / 64;
+  const int tall = (long long)rows_capacity > (long long)N;   // which operand is the big one
+  const long long blocks = tall ? (long long)((nbm + 7) / 8) * 8 * ncb : (long long)((ncb + 7) / 8) * 8 * nbm;
+  PCNN_LAUNCH(fc_rows_mfma_kernel, dim3((unsigned)blocks, smax), dim3(512), 0, stream, x, wt, bias, addend, y, in_features, N,
+              rows_capacity, relu, num_rows_dev, nbm, ncb, tall, part, smax, wscap, ldy, nvalid, y2, split_col, y_b, relu_b);
+  *launched = true;
+  return PCNN_OK;
+}
+
 }  // namespace
 
 extern "C" int pcnn_fc_rows_workspace_bytes(int rows_capacity, int in_features, int out_features, size_t* bytes)
@@ -333,39 +348,37 @@ extern "C" int pcnn_fc_rows_fwd(const float* x, const float* wt, const float* bi
                                 const float* addend, float* y, void* workspace, size_t workspace_bytes,
                                 void* stream_)
 {
-  PCNN_REQUIRE(rows_capacity >= 0, PCNN_EINVAL, "fc_rows: negative row capacity");
-  PCNN_REQUIRE(in_features >= 128 && in_features % 64 == 0, PCNN_EINVAL,
-               "fc_rows: in_features must be a multiple of 64, >= 128 (got %d)", in_features);
-  PCNN_REQUIRE(out_features >= 64 && out_features % 64 == 0, PCNN_EINVAL,
-               "fc_rows: out_features must be a multiple of 64 (got %d)", out_features);
-  if (rows_capacity == 0) return PCNN_OK;
-  PCNN_REQUIRE(x && wt && bias && y, PCNN_ENULL, "fc_rows: NULL pointer");
-  PCNN_REQUIRE(aligned16(x) && aligned16(wt) && aligned16(y) && aligned16(addend) && aligned16(bias), PCNN_EINVAL,
-               "fc_rows: pointers (x, wt, bias, addend, y) must be 16-byte aligned");
-  PCNN_REQUIRE((long long)rows_capacity * in_features < (1ll << 30) && (long long)out_features * in_features < (1ll << 30),
-               PCNN_EINVAL, "fc_rows: operand larger than the 32-bit byte offsets of the kernel");
   hipStream_t stream = (hipStream_t)stream_;
-  const int nbm = (rows_capacity + 63) / 64, ncb = out_features / 64;
-  const int tall = (long long)rows_capacity > (long long)out_features;   // which operand is the big one
-  const long long blocks = tall ? (long long)((nbm + 7) / 8) * 8 * ncb : (long long)((ncb + 7) / 8) * 8 * nbm;
-  // split-K for launches with few live rows (decided on the device): needs the caller's workspace
-  const int ws_rows = rows_capacity < FC_WS_ROWS ? (rows_capacity + 63) / 64 * 64 : FC_WS_ROWS;
+  // split-K for launches with few live rows (decided on the device): needs the caller's workspace. (The arguments are
+  // checked in fc_rows_launch, after this: `rows` keeps the arithmetic defined for a capacity that will be refused.)
+  const int rows = std::max(rows_capacity, 0);
+  const int ws_rows = rows < FC_WS_ROWS ? (rows + 63) / 64 * 64 : FC_WS_ROWS;
   const size_t need = sizeof(float) * (size_t)FC_SMAX * ws_rows * out_features;
   // grid.y = the most splits a launch may use; every split of every block is a workgroup that must at least
   // be launched to find out that it has nothing to do: a big capacity (train mode: 48 x 64 blocks) gets 2 — what
   // the balance split above can use — and a small one up to FC_SMAX
   // (a short-K layer — fc7: 64 stages — never takes the balance split: no second grid row, no reduction launch for it)
   const long long floor_s = in_features / 64 >= 128 ? 2 : 1;
-  const int smax_cap = (int)std::min<long long>(FC_SMAX, std::max<long long>(floor_s, 4096 / ((long long)nbm * ncb)));
+  const long long wgs = (long long)((rows + 63) / 64) * (out_features / 64);   // workgroups per split (0: nothing will be launched)
+  const int smax_cap = wgs > 0 ? (int)std::min<long long>(FC_SMAX, std::max<long long>(floor_s, 4096 / wgs)) : 1;
   const int smax = (workspace && workspace_bytes >= need && fc_can_split(rows_capacity, in_features, out_features) && aligned16(workspace)) ? smax_cap : 1;
   float* part = smax > 1 ? static_cast<float*>(workspace) : nullptr;
   const int wscap = FC_SMAX * ws_rows;   // rows of partial outputs the workspace holds
-  PCNN_LAUNCH(fc_rows_mfma_kernel, dim3((unsigned)blocks, smax), dim3(512), 0, stream, x, wt, bias, addend, y, in_features,
-              out_features, rows_capacity, relu, num_rows_dev, nbm, ncb, tall, part, smax, wscap, out_features, out_features, (float*)nullptr, 0, (float*)nullptr, 0);
+  auto own_checks = [&] {
+    PCNN_REQUIRE(out_features >= 64 && out_features % 64 == 0, PCNN_EINVAL,
+                 "fc_rows: out_features must be a multiple of 64 (got %d)", out_features);
+    return PCNN_OK;
+  };
+  bool launched;
+  const int st = fc_rows_launch("fc_rows", own_checks, x && wt && bias && y,
+                                aligned16(x) && aligned16(wt) && aligned16(y) && aligned16(addend) && aligned16(bias), "x, wt, bias, addend, y",
+                                &launched, x, wt, bias, addend, y, rows_capacity, in_features, out_features, relu, num_rows_dev, part, smax,
+                                wscap, out_features, out_features, nullptr, 0, nullptr, 0, stream);
+  if (!launched) return st;
   if (smax > 1) {
     const long long items = (long long)std::min(rows_capacity, wscap / 2) * (out_features / 4);   // (a split launch has at most wscap / 2 live rows)
     PCNN_LAUNCH(fc_rows_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, part, bias, addend, y,
-                in_features, out_features, rows_capacity, relu, num_rows_dev, ncb, smax, wscap);
+                in_features, out_features, rows_capacity, relu, num_rows_dev, out_features / 64, smax, wscap);
   }
   return check_launch("fc_rows_fwd");
 }
@@ -379,27 +392,19 @@ extern "C" int pcnn_fc_rows_cols_fwd(const float* x, const float* wt, const floa
                                      int in_features, int out_padded, int out_features, int activation,
                                      const int32_t* num_rows_dev, float* y, float* y_tanh, void* stream_)
 {
-  PCNN_REQUIRE(rows_capacity >= 0, PCNN_EINVAL, "fc_rows_cols: negative row capacity");
-  PCNN_REQUIRE(in_features >= 128 && in_features % 64 == 0, PCNN_EINVAL,
-               "fc_rows_cols: in_features must be a multiple of 64, >= 128 (got %d)", in_features);
-  PCNN_REQUIRE(out_padded >= 64 && out_padded % 64 == 0, PCNN_EINVAL, "fc_rows_cols: out_padded must be a multiple of 64 (got %d)", out_padded);
-  PCNN_REQUIRE(out_features >= 4 && out_features % 4 == 0 && out_features <= out_padded && out_features > out_padded - 64, PCNN_EINVAL,
-               "fc_rows_cols: out_features must be a multiple of 4 inside the last 64-column block of out_padded (got %d of %d)", out_features, out_padded);
-  PCNN_REQUIRE(activation >= 0 && activation <= 2, PCNN_EINVAL, "fc_rows_cols: activation 0 (none), 1 (ReLU) or 2 (tanh)");
-  if (rows_capacity == 0) return PCNN_OK;
-  PCNN_REQUIRE(x && wt && bias && y && (activation != 2 || y_tanh), PCNN_ENULL, "fc_rows_cols: NULL pointer");
-  PCNN_REQUIRE(aligned16(x) && aligned16(wt) && aligned16(y) && aligned16(y_tanh) && aligned16(bias), PCNN_EINVAL,
-               "fc_rows_cols: pointers (x, wt, bias, y, y_tanh) must be 16-byte aligned");
-  PCNN_REQUIRE((long long)rows_capacity * in_features < (1ll << 30) && (long long)out_padded * in_features < (1ll << 30),
-               PCNN_EINVAL, "fc_rows_cols: operand larger than the 32-bit byte offsets of the kernel");
-  hipStream_t stream = (hipStream_t)stream_;
-  const int nbm = (rows_capacity + 63) / 64, ncb = out_padded / 64;
-  const int tall = (long long)rows_capacity > (long long)out_padded;
-  const long long blocks = tall ? (long long)((nbm + 7) / 8) * 8 * ncb : (long long)((ncb + 7) / 8) * 8 * nbm;
-  PCNN_LAUNCH(fc_rows_mfma_kernel, dim3((unsigned)blocks, 1), dim3(512), 0, stream, x, wt, bias, (const float*)nullptr, y, in_features,
-              out_padded, rows_capacity, activation == 1 ? 1 : 0, num_rows_dev, nbm, ncb, tall, (float*)nullptr, 1, 0, out_features, out_features,
-              activation == 2 ? y_tanh : (float*)nullptr, 0, (float*)nullptr, 0);
-  return check_launch("fc_rows_cols_fwd");
+  auto own_checks = [&] {
+    PCNN_REQUIRE(out_padded >= 64 && out_padded % 64 == 0, PCNN_EINVAL, "fc_rows_cols: out_padded must be a multiple of 64 (got %d)", out_padded);
+    PCNN_REQUIRE(out_features >= 4 && out_features % 4 == 0 && out_features <= out_padded && out_features > out_padded - 64, PCNN_EINVAL,
+                 "fc_rows_cols: out_features must be a multiple of 4 inside the last 64-column block of out_padded (got %d of %d)", out_features, out_padded);
+    PCNN_REQUIRE(activation >= 0 && activation <= 2, PCNN_EINVAL, "fc_rows_cols: activation 0 (none), 1 (ReLU) or 2 (tanh)");
+    return PCNN_OK;
+  };
+  bool launched;
+  const int st = fc_rows_launch("fc_rows_cols", own_checks, x && wt && bias && y && (activation != 2 || y_tanh),
+                                aligned16(x) && aligned16(wt) && aligned16(y) && aligned16(y_tanh) && aligned16(bias), "x, wt, bias, y, y_tanh",
+                                &launched, x, wt, bias, nullptr, y, rows_capacity, in_features, out_padded, activation == 1 ? 1 : 0, num_rows_dev,
+                                nullptr, 1, 0, out_features, out_features, activation == 2 ? y_tanh : nullptr, 0, nullptr, 0, (hipStream_t)stream_);
+  return launched ? check_launch("fc_rows_cols_fwd") : st;
 }
 
 // Two layers on the same rows as ONE product (round 5: score_conv4 [ReLU] and score_conv4_vertex [none] both read conv4_3,
@@ -410,24 +415,16 @@ extern "C" int pcnn_fc_rows_split_fwd(const float* x, const float* wt, const flo
                                       int out_a, int out_b, int relu_a, int relu_b, const int32_t* num_rows_dev,
                                       float* y_a, float* y_b, void* stream_)
 {
-  PCNN_REQUIRE(rows_capacity >= 0, PCNN_EINVAL, "fc_rows_split: negative row capacity");
-  PCNN_REQUIRE(in_features >= 128 && in_features % 64 == 0, PCNN_EINVAL,
-               "fc_rows_split: in_features must be a multiple of 64, >= 128 (got %d)", in_features);
-  PCNN_REQUIRE(out_a >= 64 && out_a % 64 == 0 && out_b >= 64 && out_b % 64 == 0, PCNN_EINVAL,
-               "fc_rows_split: both widths must be multiples of 64 (got %d, %d)", out_a, out_b);
-  if (rows_capacity == 0) return PCNN_OK;
-  PCNN_REQUIRE(x && wt && bias && y_a && y_b, PCNN_ENULL, "fc_rows_split: NULL pointer");
-  PCNN_REQUIRE(aligned16(x) && aligned16(wt) && aligned16(y_a) && aligned16(y_b) && aligned16(bias), PCNN_EINVAL,
-               "fc_rows_split: pointers (x, wt, bias, y_a, y_b) must be 16-byte aligned");
+  auto own_checks = [&] {
+    PCNN_REQUIRE(out_a >= 64 && out_a % 64 == 0 && out_b >= 64 && out_b % 64 == 0, PCNN_EINVAL,
+                 "fc_rows_split: both widths must be multiples of 64 (got %d, %d)", out_a, out_b);
+    return PCNN_OK;
+  };
   const int N = out_a + out_b;
-  PCNN_REQUIRE((long long)rows_capacity * in_features < (1ll << 30) && (long long)N * in_features < (1ll << 30),
-               PCNN_EINVAL, "fc_rows_split: operand larger than the 32-bit byte offsets of the kernel");
-  hipStream_t stream = (hipStream_t)stream_;
-  const int nbm = (rows_capacity + 63) / 64, ncb = N / 64;
-  const int tall = (long long)rows_capacity > (long long)N;
-  const long long blocks = tall ? (long long)((nbm + 7) / 8) * 8 * ncb : (long long)((ncb + 7) / 8) * 8 * nbm;
-  PCNN_LAUNCH(fc_rows_mfma_kernel, dim3((unsigned)blocks, 1), dim3(512), 0, stream, x, wt, bias, (const float*)nullptr, y_a, in_features,
-              N, rows_capacity, relu_a ? 1 : 0, num_rows_dev, nbm, ncb, tall, (float*)nullptr, 1, 0, out_a, N, (float*)nullptr, out_a, y_b,
-              relu_b ? 1 : 0);
-  return check_launch("fc_rows_split_fwd");
+  bool launched;
+  const int st = fc_rows_launch("fc_rows_split", own_checks, x && wt && bias && y_a && y_b,
+                                aligned16(x) && aligned16(wt) && aligned16(y_a) && aligned16(y_b) && aligned16(bias), "x, wt, bias, y_a, y_b",
+                                &launched, x, wt, bias, nullptr, y_a, rows_capacity, in_features, N, relu_a ? 1 : 0, num_rows_dev, nullptr, 1, 0,
+                                out_a, N, nullptr, out_a, y_b, relu_b ? 1 : 0, (hipStream_t)stream_);
+  return launched ? check_launch("fc_rows_split_fwd") : st;
 }

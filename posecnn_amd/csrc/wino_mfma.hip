@@ -12,9 +12,8 @@
 //
 //  * Workgroup = 32 tiles x 64 output channels, 4 waves, TWO workgroups per CU (one wave of each per
 //    SIMD, so that one workgroup's LDS / global / VALU work, barrier waits and epilogue hide under the
-//    other's MFMAs; the 64-tile / 8-wave / one-per-CU shape, WR = 2, measures 2-7 % slower and is kept
-//    for the ablation harness). Wave wn owns the block's 32 tiles x channels [16 wn, 16 wn + 16): two
-//    16x16 accumulator blocks.
+//    other's MFMAs). Wave w owns the block's 32 tiles x channels [16 w, 16 w + 16): two 16x16
+//    accumulator blocks. This is the only shape; what else was measured is listed at the kernel.
 //  * The transform-domain product M NEVER exists, not even in registers as a whole: planes are
 //    processed column by column (nu outer, xi inner). Once the 6 planes of column nu are summed
 //    over all of Cin, t = A^T M[:, nu] (4 values) is folded into the 16 outputs Y += t (x) A[nu, :]
@@ -22,18 +21,16 @@
 //    lets 64 x 64 elements per CU (two 32 x 64 blocks) fit the register file (360 KB of the CU's
 //    512 KB) — 4x the tile of the round-1 kernel.
 //  * Operands go global -> LDS directly (global_load_lds_dwordx4: no staging registers, no
-//    ds_write pass) through a ring of 3 stage buffers, ONE barrier per 64-deep K stage: the 4 DMA
-//    instructions a wave issues for stage s+2 fly under the MFMAs of stages s and s+1 (a stage of a
-//    Cin = 64 layer is a fresh HBM miss per plane: one stage of cover is not enough). The barrier
-//    is a raw s_barrier behind a COUNTED s_waitcnt vmcnt(4) — __syncthreads() would drain the DMA
-//    queue (vmcnt(0)) every stage. The LDS image is the DMA's
-//    lane-linear one (rows of 64 floats, unpadded); bank conflicts are avoided by an XOR swizzle of
-//    the 16-byte chunk index with the row (applied to the SOURCE address of the DMA and to the
-//    ds_read_b128 address — the same involution on both sides). One b128 read feeds 4 MFMAs (K is
-//    consumed in the order 16 j + 4 (lane >> 4) + i for both operands). A lane's 8 read addresses are
-//    loop invariants: the ring position travels in the reads' offset field (three copies of a half
-//    stage's six reads behind a scalar branch), so a stage has NO vector-ALU instruction between its
-//    32 MFMAs — on gfx950 a VALU instruction is never hidden behind an MFMA of its SIMD.
+//    ds_write pass) through a ring of 3 stage buffers, ONE barrier per 64-deep K stage: the 6 DMA
+//    instructions a wave issues for stage s+2 (2 of V rows, 4 of U^T rows) fly under the MFMAs of
+//    stages s and s+1 (a stage of a Cin = 64 layer is a fresh HBM miss per plane: one stage of cover
+//    is not enough). The barrier is a raw s_barrier behind a COUNTED s_waitcnt vmcnt(6) — the wave's
+//    own DMAs of stage s have landed, the 6 of stage s+1 stay in flight; __syncthreads() would drain
+//    the DMA queue (vmcnt(0)) every stage. The LDS image, its XOR swizzle and the rules of the ring
+//    are those of csrc/mfma_ring.h, shared with csrc/fc_mfma.hip. One b128 read feeds 4 MFMAs. A
+//    lane's 8 read addresses are loop invariants: the ring position travels in the reads' offset field
+//    (three copies of a half stage's six reads behind a scalar branch), so a stage has NO vector-ALU
+//    instruction between its 32 MFMAs.
 //  * Epilogue: bias + ReLU (+ 2x2 max-pool of the 4x4 tile) in registers, then through LDS (two staging
 //    buffers, one barrier per pass) so that every store instruction writes whole 256-byte channel rows
 //    (the C/D layout alone would give 64-byte segments).
@@ -48,85 +45,64 @@
 #include <cstdlib>
 
 #include "pcnn_device.h"
+#include "mfma_ring.h"
 
 namespace {
 
 using namespace pcnn;
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int WM_BC = 64;     // output channels per workgroup
 constexpr int WM_KC = 64;     // K (input channels) per pipeline stage
 constexpr int WM_LD = 64;     // LDS row (floats): unpadded, XOR-swizzled 16-byte chunks
 constexpr int WM_NBUF = 3;    // stage buffers in the LDS ring (prefetch distance 2)
+constexpr int WM_BT = 32;     // tiles per workgroup
+constexpr int WM_NW = 4;      // waves per workgroup
+constexpr int WM_UB = WM_BC / 4 / WM_NW;   // U^T DMA instructions (4 rows each) per wave and stage: 4, next to 2 of V rows
 
-// 16 bytes per lane, global -> LDS, no register round trip. LDS destination = wave-uniform base +
-// 16 * lane (so the image is lane-linear); the per-lane SOURCE address carries the swizzle.
-__device__ __forceinline__ void glds16(const char* g, float* lds_wave_base)
-{
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// The same DMA with the addressing spelled out: SGPR base + 32-bit VGPR byte offset, LDS base in M0. Through
-// the builtin the compiler turned most of these into 64-bit VGPR addresses (a v_mov_b64 + v_lshl_add_u64 pair
-// per load, ~20 VALU instructions per stage next to 32 MFMAs); here the per-stage pointer arithmetic stays on
-// the scalar unit. Completion is tracked by the hand-placed s_waitcnt vmcnt(N) of the stage barrier.
-__device__ __forceinline__ void glds16_s(const char* sbase, unsigned voff, unsigned lds_addr)
-{
-  asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(lds_addr) : "memory", "m0");
-}
-
-// Output transform, one column of the 6x6 transform domain at a time:
-//   t = A^T m   with A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
-__device__ __forceinline__ void at6_col(const float* m, float* t)
-{
-  const float s = m[1] + m[2], d = m[1] - m[2], S = m[3] + m[4], D = m[3] - m[4];
-  t[0] = (m[0] + s) + S;
-  t[1] = __builtin_fmaf(2.f, D, d);     // (explicit FMAs: this file is built -ffp-contract=off; the fold is 12 %
-  t[2] = __builtin_fmaf(4.f, S, s);     //  of a Cin = 64 layer, and one instruction per term instead of two
-  t[3] = __builtin_fmaf(8.f, D, d) + m[5];   // buys 1.7 % of the 12-layer trunk)
-}
+// The bits of the kernel's ABL parameter (tools/wino_ablate.hip only; the library instantiates 0): each leaves one
+// ingredient out to see what it costs. Timing only — the results are wrong by design.
+enum : int {
+  ABL_NO_BARRIER = 1,       // the stage's counted wait without its s_barrier
+  ABL_NO_DMA = 2,           // no operand DMA
+  ABL_NO_LDS_READS = 4,     // no ds_read_b128 (the operand registers stay what they are)
+  ABL_NO_MFMA = 8,          // no MFMAs
+  ABL_NO_FOLD = 16,         // no column fold
+  ABL_NO_EPILOGUE = 32,     // no epilogue: one value per lane keeps the accumulators alive
+  ABL_L2_OPERANDS = 64,     // every workgroup on the operands of block (0, 0): all L2-resident, i.e. what the fabric costs
+  ABL_NO_STORES = 128,      // unpooled output (POOL 0 / 2): the staged rows are read back but not stored
+  ABL_EPI_REGS_ONLY = 256,  // epilogue = bias + ReLU on the registers, nothing staged or stored
+  ABL_NT_STORES = 512,      // unpooled output: non-temporal stores
+};
 
 // POOL: 0 = y [.,H,W,Cout]; 1 = only max_pool_2x2(y) (written to y); 2 = both (y and ypool)
-// WR: wave rows — 1 (what the library launches): 32 tiles x 64 channels, 4 waves, two workgroups per CU;
-// 2: 64 x 64, 8 waves, one workgroup per CU (kept for the ablation harness; see the launcher for the numbers).
-// ABL (tools/wino_ablate.hip only; the library instantiates 0): leave one ingredient of the K loop out to
-// see what it costs — 1 no barrier, 2 no DMA, 4 no LDS reads, 8 no MFMAs, 16 no column fold, 32 no epilogue, 64 every
-// workgroup on the operands of block (0, 0) (L2-resident: what the fabric costs).
-// ZC (round 4): the first MFMA pair into a plane's accumulators takes C = 0 as an inline constant instead of reading
-// registers that a v_mov zeroed after every column fold (48 VALU per fold; on the Cin = 64 layers a fold comes every 6
-// stages and VALU time is paid in full next to the MFMAs). Same bits: 0 + a b either way.
+// ABL: see above.
 // `mode` bit 0: XCD x owns channel block x (launches with ncb == 8 whose filter bank outweighs their transformed input,
 // i.e. the deep layers of a single frame: every XCD then streams ITS eighth of U once instead of all of U).
-// Measured and dropped in round 4 (tools/archive/r4_wino_modes.sh, 12-layer totals at 2 x 16 frames):
+// The first MFMA pair into a plane's accumulators takes C = 0 as an inline constant, so a column fold leaves them as they are.
+// Measured and dropped — what was tried and what it measured (12-layer totals are at 2 x 16 frames). The code of the
+// template switches WR, ZC and EPI was last in the tree at commit 73cff15; the two round-4 schedules left it in round 5:
+//   * WR = 2 (round 2): 64 tiles x 64 channels, 8 waves, ONE workgroup per CU, 2/3 of the operand bytes per flop: conv3_2
+//     1.87 ms against 1.75 for the pairs, conv3_1 1.02 / 0.95, conv4_2 1.79 / 1.78, 12 layers 16.25 / 15.86 ms.
+//   * ZC = 0 (round 3): a v_mov zeroing the accumulators after every column fold (48 VALU per fold) instead of the inline
+//     constant: same bits (0 + a b either way), 12 layers 14.56-14.64 ms against 14.62.
 //   * s_setprio 3 / 0 by the workgroup's slot on the CU (HW_ID.TG_ID), so that one of the two co-resident workgroups runs
-//     as if alone and the other fills the matrix pipe's gaps: 14.62 -> 14.71 / 14.90 ms for the two polarities — the
-//     symmetric pair is the better schedule;
-//   * persistent workgroups (a grid of the 512 resident slots, each walking its (tile block, channel block) pairs, so that
-//     the early layers' 36-72-stage pairs stop paying a dispatch, a cold prologue and a store drain each): 14.62 -> 15.07 ms
-//     (conv4_2 1.61 -> 1.73, conv2_2 1.74 -> 1.83) — the hardware's dynamic hand-out of pairs to whichever slot frees first
-//     balances better than a static walk, and the 8 extra live registers of the loop cost the kernel its last slack.
-// EPI (round 5; not instantiated by the library — tools/wino_ablate.hip can): 1 = the MFMA operand roles swapped (A = U^T rows,
-// B = V rows: the same products in the same K order, so the same bits — verified against EPI = 0 on seven layer shapes, all pool
-// modes, both block maps) — a lane then holds FOUR CONSECUTIVE CHANNELS of one tile instead of one channel of four tiles, and the
-// epilogue stores its outputs straight from registers as 16-byte pieces (16 lanes x 4 quads = a tile's 64 channels per 256
-// bytes): no LDS staging, no barriers. The warm ablation had priced the staging at 7 / 5 / 4 % of conv2_1 / conv2_2 / conv3_2;
-// measured, the direct form gives it back in 64-byte partial-line stores: 12 layers 14.136 vs 14.169 ms alone (conv2_1 1.052
-// vs 1.022, conv2_2 1.656 vs 1.676, conv3_1 0.868 vs 0.885, conv4_2 1.569 vs 1.589), the kernel inside the step 1107 / 1118 vs
-// 1098 / 1098 us per launch, the step 796 / 794 vs 764 / 808 frames/s: no gain — the staged epilogue (0) stays.
-template <int POOL, int WR, int ABL = 0, int ZC = 1, int EPI = 0>
-__global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
+//     as if alone and the other fills the gaps: 14.62 -> 14.71 / 14.90 ms for the two polarities.
+//   * persistent workgroups (a grid of the 512 resident slots, each walking its block pairs): 14.62 -> 15.07 ms (conv4_2
+//     1.61 -> 1.73, conv2_2 1.74 -> 1.83) — the hardware's hand-out of blocks to whichever slot frees first balances better
+//     than a static walk, and the loop's 8 extra live registers cost the kernel its last slack.
+//   * EPI = 1 (round 5): MFMA operand roles swapped (same products, same K order, same bits), so that a lane holds four
+//     consecutive channels of one tile and stores 16-byte pieces straight from registers — no LDS staging, no barriers. The
+//     ablation had priced the staging at 7 / 5 / 4 % of conv2_1 / conv2_2 / conv3_2; the direct form gives it back in
+//     64-byte partial-line stores: 12 layers 14.136 against 14.169 ms alone, inside the step 1107 / 1118 against 1098 /
+//     1098 us per launch, the step 796 / 794 against 764 / 808 frames/s. No gain: the staged epilogue stays.
+template <int POOL, int ABL = 0>
+__global__ __launch_bounds__(64 * WM_NW, 2) void wino43_mfma_kernel(
     const float* __restrict__ v, const float* __restrict__ ut, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ ypool, int H, int W, int Cin, int Cout, int Ht, int Wt,
     long long T, long long tiles_per_group, int relu, int nbt, int ncb, int ksplit, long long ysplit_stride, int mode)
 {
-  constexpr int BT = 32 * WR, NW = 4 * WR, NT = 256 * WR;
-  constexpr int RING = WM_NBUF * (BT + 64) * WM_LD, STAGE2 = 2 * BT * 4 * 64;
-  __shared__ __attribute__((aligned(16))) float smem[RING > STAGE2 ? RING : STAGE2];   // sA[3][BT][64] | sB[3][64][64]; epilogue: 2 x [BT][4][64]
-  float(*sA)[BT][WM_LD] = reinterpret_cast<float(*)[BT][WM_LD]>(smem);
-  float(*sB)[64][WM_LD] = reinterpret_cast<float(*)[64][WM_LD]>(smem + WM_NBUF * BT * WM_LD);
+  constexpr int RING = WM_NBUF * (WM_BT + 64) * WM_LD, STAGE2 = 2 * WM_BT * 4 * 64;
+  __shared__ __attribute__((aligned(16))) float smem[RING > STAGE2 ? RING : STAGE2];   // sA[3][WM_BT][64] | sB[3][64][64]; epilogue: 2 x [WM_BT][4][64]
 
   // XCD-aware block map: XCD x = blockIdx % 8 takes tile blocks tb == x (mod 8); on an XCD the
   // channel blocks of a tile block are consecutive
@@ -135,17 +111,16 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
   const int cb = cbmajor ? x : q % ncb;
   const int tb = cbmajor ? q : (q / ncb) * 8 + x;
   if (tb >= nbt) return;
-  const int tb_data = (ABL & 64) ? 0 : tb, cb_data = (ABL & 64) ? 0 : cb;   // ABL 64 (timing only): every workgroup reads block (0, 0): all operands L2-resident
+  const int tb_data = (ABL & ABL_L2_OPERANDS) ? 0 : tb, cb_data = (ABL & ABL_L2_OPERANDS) ? 0 : cb;
   y += (long long)blockIdx.y * ysplit_stride;    // `ksplit` > 1: this Cin slice's partial output (see below)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: everything derived from it (LDS bases, M0) stays on the SALU
-  const int wm = wave & (WR - 1), wn = wave / WR;
   const int lr = lane & 15, lk = lane >> 4;
-  // tile blocks never straddle a group: group g owns tiles [g tpg, (g+1) tpg) in nbg blocks of 64
-  const int nbg = (int)((tiles_per_group + BT - 1) / BT);
+  // tile blocks never straddle a group: group g owns tiles [g tpg, (g+1) tpg) in nbg blocks of WM_BT
+  const int nbg = (int)((tiles_per_group + WM_BT - 1) / WM_BT);
   const int grp = tb / nbg;
-  const long long t0 = (long long)grp * tiles_per_group + (long long)(tb_data - (ABL & 64 ? 0 : grp * nbg)) * BT;
+  const long long t0 = (long long)grp * tiles_per_group + (long long)(tb_data - (ABL & ABL_L2_OPERANDS ? 0 : grp * nbg)) * WM_BT;
   const long long tend = (long long)(grp + 1) * tiles_per_group;   // first tile that is not this block's business
   const float* utg = ut + (size_t)grp * 36 * Cout * Cin;
   // `ksplit` > 1 (small launches, see the launcher): workgroup blockIdx.y contracts only its slice of Cin and
@@ -153,37 +128,35 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
   const int ks = blockIdx.y;
   const int NK = Cin / WM_KC / ksplit;
 
-  // staging: a stage = BT rows x 256 B of V and 64 rows of U^T = BT/4 + 16 DMA instructions of 4 rows
-  // each; wave w issues V instructions 2w, 2w + 1 and U^T instructions (16/NW) w ... Lane l of
+  // staging: a stage = WM_BT rows x 256 B of V and 64 rows of U^T = WM_BT/4 + 16 DMA instructions of 4 rows
+  // each; wave w issues V instructions 2w, 2w + 1 and U^T instructions WM_UB w ... WM_UB w + WM_UB - 1. Lane l of
   // instruction ii lands at row 4 ii + (l >> 4), physical chunk l & 15, and therefore fetches logical
   // chunk (l & 15) ^ (row & 15).
-  constexpr int UB = 16 / NW;                                   // U^T instructions per wave (2 or 4)
   const int dr0 = 8 * wave + lk, dr1 = dr0 + 4;                 // the lane's V rows in its two instructions
-  const int dc0 = (lr ^ (dr0 & 15)) * 4, dc1 = (lr ^ (dr1 & 15)) * 4;
-  const int ur0 = 4 * UB * wave + lk;                           // first U^T row; instruction i adds 4 i
+  const int dc0 = ring_src_col(lr, dr0), dc1 = ring_src_col(lr, dr1);
+  const int ur0 = 4 * WM_UB * wave + lk;                           // first U^T row; instruction i adds 4 i
   const long long tlast = tend - 1;
   const long long ta0 = t0 + dr0 < tend ? t0 + dr0 : tlast, ta1 = t0 + dr1 < tend ? t0 + dr1 : tlast;   // rows past the end: any finite data, never stored
   // per-lane BYTE offsets (32 bit) from wave-uniform bases: the DMA then addresses as SGPR base + VGPR
   // offset and the per-stage pointer arithmetic stays on the scalar unit
   const unsigned va0 = (unsigned)((ta0 * Cin + dc0) * 4), va1 = (unsigned)((ta1 * Cin + dc1) * 4);
-  unsigned ub[UB];
+  unsigned ub[WM_UB];
 #pragma unroll
-  for (int i = 0; i < UB; i++) ub[i] = (unsigned)((((size_t)(cb_data * WM_BC + ur0 + 4 * i)) * Cin + (lr ^ ((ur0 + 4 * i) & 15)) * 4) * 4);
+  for (int i = 0; i < WM_UB; i++) ub[i] = (unsigned)((((size_t)(cb_data * WM_BC + ur0 + 4 * i)) * Cin + ring_src_col(lr, ur0 + 4 * i)) * 4);
   const char* vbase = reinterpret_cast<const char*>(v);
   const char* ubase = reinterpret_cast<const char*>(utg);
   const long long vplane = T * Cin;
   const long long uplane = (long long)Cout * Cin;
   const int ldsw = 8 * wave * WM_LD;                            // this wave's first V row (floats) inside a stage buffer
-  const int ldsu = 4 * UB * wave * WM_LD;                       // ... and its first U^T row
+  const int ldsu = 4 * WM_UB * wave * WM_LD;                       // ... and its first U^T row
   // LDS byte addresses of those rows in stage buffer 0 (wave-uniform: M0 of the DMA)
   const unsigned lds_base_ = (unsigned)(unsigned long long)(__attribute__((address_space(3))) float*)smem;
   const unsigned lds_a0 = lds_base_ + (unsigned)ldsw * 4u;
-  const unsigned lds_b0 = lds_base_ + (unsigned)(WM_NBUF * BT * WM_LD + ldsu) * 4u;
+  const unsigned lds_b0 = lds_base_ + (unsigned)(WM_NBUF * WM_BT * WM_LD + ldsu) * 4u;
 
   // the lane's bias value, requested HERE: issued where it is first used (the epilogue, round 4) it was a bare global
   // round trip between the last MFMA and the first staged row of every workgroup (~1 us of a 15-us conv2_1 workgroup)
-  const float bv = (bias && !EPI) ? bias[(size_t)grp * Cout + cb * WM_BC + 16 * wn + lr] : 0.f;   // (no bias: the raw partial output of a Cin split)
-  const v4f bv4 = (bias && EPI) ? *reinterpret_cast<const v4f*>(bias + (size_t)grp * Cout + cb * WM_BC + 16 * wn + 4 * lk) : (v4f){0.f, 0.f, 0.f, 0.f};
+  const float bv = bias ? bias[(size_t)grp * Cout + cb * WM_BC + 16 * wave + lr] : 0.f;   // (no bias: the raw partial output of a Cin split)
   v4f acc[6][2];
 #pragma unroll
   for (int i = 0; i < 6; i++) acc[i][0] = acc[i][1] = (v4f){0.f, 0.f, 0.f, 0.f};
@@ -200,14 +173,14 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
       for (int o = 0; o < 16; o++) yo2[b][i][o] = (v2f){0.f, 0.f};
 
 #define WM_DMA(BUF, VO, UO)                                                  \
-  if constexpr (!(ABL & 2)) {                                                \
+  if constexpr (!(ABL & ABL_NO_DMA)) {                                       \
     const char* vs_ = vbase + (VO) * 4;                                      \
     const char* us_ = ubase + (UO) * 4;                                      \
-    const unsigned la_ = lds_a0 + (unsigned)(BUF) * (BT * WM_LD * 4);          \
+    const unsigned la_ = lds_a0 + (unsigned)(BUF) * (WM_BT * WM_LD * 4);       \
     const unsigned lb_ = lds_b0 + (unsigned)(BUF) * (64 * WM_LD * 4);          \
     glds16_s(vs_, va0, la_);                                                 \
     glds16_s(vs_, va1, la_ + 4 * WM_LD * 4);                                 \
-    _Pragma("unroll") for (int i_ = 0; i_ < UB; i_++)                         \
+    _Pragma("unroll") for (int i_ = 0; i_ < WM_UB; i_++)                      \
       glds16_s(us_, ub[i_], lb_ + 4 * i_ * WM_LD * 4);                        \
   }
 
@@ -235,11 +208,11 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
   int cur = 0;
 
   // ds_read side of the swizzle: row R = (..) + lr, logical chunk 4 j + lk -> physical (4 j + lk) ^ lr
-  const int ra0 = (32 * wm + lr) * WM_LD, rb = (16 * wn + lr) * WM_LD;   // (+ 16 rows for the second block)
+  const int ra0 = lr * WM_LD, rb = (16 * wave + lr) * WM_LD;   // (+ 16 rows for the second block)
 
   // The K loop is software pipelined by half a stage: the 16 MFMAs of K groups 2, 3 of stage s-1 are
   // issued AFTER the barrier of stage s, behind the LDS reads of groups 0, 1 of stage s — so the LDS
-  // latency that follows every barrier (all 8 waves would otherwise wait for their first operands at
+  // latency that follows every barrier (all waves would otherwise wait for their first operands at
   // the same moment, with the matrix pipe idle) and the latency of the mid-stage reads are both
   // covered by MFMAs that are already queued. Two operand register sets: X (groups 0, 1), Y (2, 3).
   v4f xa0[2], xa1[2], xb[2], ya0[2], ya1[2], yb[2];
@@ -251,77 +224,65 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
   unsigned adA[4], adB[4];   // byte addresses of this lane's operand chunks in stage buffer 0, per K group
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    const unsigned chb = (unsigned)(((4 * j + lk) ^ lr) * 16);
+    const unsigned chb = ring_chunk_bytes(j, lk, lr);
     adA[j] = lds0 + (unsigned)ra0 * 4u + chb;
-    adB[j] = lds0 + (unsigned)(WM_NBUF * BT * WM_LD + rb) * 4u + chb;
+    adB[j] = lds0 + (unsigned)(WM_NBUF * WM_BT * WM_LD + rb) * 4u + chb;
   }
-// The ring position is part of the INSTRUCTION, not of the address (WR == 1): buffer `cur` of the A operand starts
+// The ring position is part of the INSTRUCTION, not of the address: buffer `cur` of the A operand starts
 // cur * 8192 bytes behind buffer 0 (second row block + 4096), of the B operand cur * 16384 — at most 32 768, inside
 // ds_read_b128's 16-bit offset field — so the lane's 8 chunk addresses adA / adB are loop invariants and a stage
 // reads with no vector arithmetic at all (the 8 v_add_u32 per stage of rounds 2-6 each cost ~3.5 cycles of matrix
 // time: a VALU instruction never hides behind an MFMA of its SIMD). The six reads of a half stage exist once per ring
 // position and `cur` (wave-uniform, on the scalar unit) picks the copy with a scalar branch; everything else of the stage
-// exists once. WR == 2 (64 KB of ring: the sums pass 65 535) keeps the add, and so does the ablation without LDS reads.
+// exists once.
 #define WM_DSREAD(DST, ADDR, OFF)                                                                     \
-  if constexpr (!(ABL & 4)) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "i"(OFF)); \
+  if constexpr (!(ABL & ABL_NO_LDS_READS)) RING_DSREAD_B128(DST, ADDR, OFF);                          \
   else asm volatile("" : "+v"(DST) : "v"(ADDR))
 #define WM_READ_AT(SA0, SA1, SB, G0, CUR)                                                             \
   _Pragma("unroll") for (int g_ = 0; g_ < 2; g_++) {                                                  \
     WM_DSREAD(SB[g_], adB[(G0) + g_], (CUR) * (64 * WM_LD * 4));                                      \
-    WM_DSREAD(SA0[g_], adA[(G0) + g_], (CUR) * (BT * WM_LD * 4));                                     \
-    WM_DSREAD(SA1[g_], adA[(G0) + g_], (CUR) * (BT * WM_LD * 4) + 4096);   /* 16 rows further */       \
+    WM_DSREAD(SA0[g_], adA[(G0) + g_], (CUR) * (WM_BT * WM_LD * 4));                                  \
+    WM_DSREAD(SA1[g_], adA[(G0) + g_], (CUR) * (WM_BT * WM_LD * 4) + 4096);   /* 16 rows further */    \
   }
 #define WM_READ(SA0, SA1, SB, G0)                                                                     \
-  if constexpr (WR == 1 && !(ABL & 4)) {                                                              \
-    if (cur == 0) { WM_READ_AT(SA0, SA1, SB, G0, 0); }                                                \
-    else if (cur == 1) { WM_READ_AT(SA0, SA1, SB, G0, 1); }                                           \
-    else { WM_READ_AT(SA0, SA1, SB, G0, 2); }                                                         \
-  } else {                                                                                            \
-    const unsigned curA = (unsigned)cur * (BT * WM_LD * 4), curB = (unsigned)cur * (64 * WM_LD * 4);  \
-    _Pragma("unroll") for (int g_ = 0; g_ < 2; g_++) {                                                \
-      const unsigned aa_ = adA[(G0) + g_] + curA, ab_ = adB[(G0) + g_] + curB;                         \
-      WM_DSREAD(SB[g_], ab_, 0);                                                                      \
-      WM_DSREAD(SA0[g_], aa_, 0);                                                                     \
-      WM_DSREAD(SA1[g_], aa_, 4096);   /* 16 rows further */                                           \
-    }                                                                                                 \
-  }
+  if constexpr (ABL & ABL_NO_LDS_READS) { WM_READ_AT(SA0, SA1, SB, G0, 0); }   /* (nothing to dispatch) */ \
+  else if (cur == 0) { WM_READ_AT(SA0, SA1, SB, G0, 0); }                                             \
+  else if (cur == 1) { WM_READ_AT(SA0, SA1, SB, G0, 1); }                                             \
+  else { WM_READ_AT(SA0, SA1, SB, G0, 2); }
+  static_assert(WM_NBUF == 3, "WM_READ dispatches over a ring of three buffers");
 #define WM_MFMA1(SA0, SA1, SB, G, ACC)                                                                \
-  if constexpr (ABL & 8) { asm volatile("" :: "v"(SA0[G]), "v"(SA1[G]), "v"(SB[G])); } else           \
+  if constexpr (ABL & ABL_NO_MFMA) { asm volatile("" :: "v"(SA0[G]), "v"(SA1[G]), "v"(SB[G])); } else \
   _Pragma("unroll") for (int i_ = 0; i_ < 4; i_++) {                                                  \
-    ACC[0] = EPI ? __builtin_amdgcn_mfma_f32_16x16x4f32(SB[G][i_], SA0[G][i_], ACC[0], 0, 0, 0)       \
-                 : __builtin_amdgcn_mfma_f32_16x16x4f32(SA0[G][i_], SB[G][i_], ACC[0], 0, 0, 0);      \
-    ACC[1] = EPI ? __builtin_amdgcn_mfma_f32_16x16x4f32(SB[G][i_], SA1[G][i_], ACC[1], 0, 0, 0)       \
-                 : __builtin_amdgcn_mfma_f32_16x16x4f32(SA1[G][i_], SB[G][i_], ACC[1], 0, 0, 0);      \
+    ACC[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(SA0[G][i_], SB[G][i_], ACC[0], 0, 0, 0);            \
+    ACC[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(SA1[G][i_], SB[G][i_], ACC[1], 0, 0, 0);            \
   }
 #define WM_MFMA(SA0, SA1, SB, ACC)                                                                    \
   WM_MFMA1(SA0, SA1, SB, 0, ACC) WM_MFMA1(SA0, SA1, SB, 1, ACC)
   /* the same K group, but the first pair starts the accumulators from the constant 0 (first MFMAs of a plane) */
 #define WM_MFMA1_Z(SA0, SA1, SB, G, ACC)                                                              \
-  if constexpr (ABL & 8) { asm volatile("" :: "v"(SA0[G]), "v"(SA1[G]), "v"(SB[G])); } else {         \
+  if constexpr (ABL & ABL_NO_MFMA) { asm volatile("" :: "v"(SA0[G]), "v"(SA1[G]), "v"(SB[G])); } else { \
     const v4f z_ = (v4f){0.f, 0.f, 0.f, 0.f};                                                         \
-    ACC[0] = EPI ? __builtin_amdgcn_mfma_f32_16x16x4f32(SB[G][0], SA0[G][0], z_, 0, 0, 0)             \
-                 : __builtin_amdgcn_mfma_f32_16x16x4f32(SA0[G][0], SB[G][0], z_, 0, 0, 0);            \
-    ACC[1] = EPI ? __builtin_amdgcn_mfma_f32_16x16x4f32(SB[G][0], SA1[G][0], z_, 0, 0, 0)             \
-                 : __builtin_amdgcn_mfma_f32_16x16x4f32(SA1[G][0], SB[G][0], z_, 0, 0, 0);            \
+    ACC[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(SA0[G][0], SB[G][0], z_, 0, 0, 0);                  \
+    ACC[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(SA1[G][0], SB[G][0], z_, 0, 0, 0);                  \
     _Pragma("unroll") for (int i_ = 1; i_ < 4; i_++) {                                                \
-      ACC[0] = EPI ? __builtin_amdgcn_mfma_f32_16x16x4f32(SB[G][i_], SA0[G][i_], ACC[0], 0, 0, 0)     \
-                   : __builtin_amdgcn_mfma_f32_16x16x4f32(SA0[G][i_], SB[G][i_], ACC[0], 0, 0, 0);    \
-      ACC[1] = EPI ? __builtin_amdgcn_mfma_f32_16x16x4f32(SB[G][i_], SA1[G][i_], ACC[1], 0, 0, 0)     \
-                   : __builtin_amdgcn_mfma_f32_16x16x4f32(SA1[G][i_], SB[G][i_], ACC[1], 0, 0, 0);    \
+      ACC[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(SA0[G][i_], SB[G][i_], ACC[0], 0, 0, 0);          \
+      ACC[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(SA1[G][i_], SB[G][i_], ACC[1], 0, 0, 0);          \
     }                                                                                                 \
   }
   // column NU of the transform domain is complete: t = A^T M[:, NU]; Y[a][e] += t[a] * A[NU][e]
   // with A[NU][:] = (1,0,0,0) (1,1,1,1) (1,-1,1,-1) (1,2,4,8) (1,-2,4,-8) (0,0,0,1); accumulators recycled
 #define WM_FOLD(NU)                                                                                   \
-  if constexpr (!(ABL & 16)) {                                                                        \
+  if constexpr (!(ABL & ABL_NO_FOLD)) {                                                               \
     const int n_ = (NU);                                                                              \
     const float c0 = n_ == 5 ? 0.f : 1.f;                                                             \
     const float c1 = n_ == 1 ? 1.f : n_ == 2 ? -1.f : n_ == 3 ? 2.f : n_ == 4 ? -2.f : 0.f;           \
     const float c2 = (n_ == 1 || n_ == 2) ? 1.f : (n_ == 3 || n_ == 4) ? 4.f : 0.f;                   \
     const float c3 = n_ == 1 ? 1.f : n_ == 2 ? -1.f : n_ == 3 ? 8.f : n_ == 4 ? -8.f : n_ == 5 ? 1.f : 0.f; \
     /* two C/D rows at a time on packed f32 (round 5): v_pk_add / v_pk_fma on the register pairs as the MFMA delivers them,  */ \
-    /* element for element at6_col + the 16 rank-1 FMAs of rounds 2-4 (same bits; 12 layers 14.5 vs 14.7 ms alone, the    */ \
-    /* step unchanged: 793 / 796 vs 792 / 794 frames/s)                                                                    */ \
+    /* element for element t = A^T m of rounds 2-4, A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1], and   */ \
+    /* their 16 rank-1 FMAs (same bits; 12 layers 14.5 vs 14.7 ms alone, the step unchanged: 793 / 796 vs 792 / 794         */ \
+    /* frames/s). Explicit FMAs: this file is built -ffp-contract=off; one instruction per term instead of two buys 1.7 %   */ \
+    /* of the 12-layer trunk (the fold is 12 % of a Cin = 64 layer)                                                         */ \
     _Pragma("unroll") for (int b_ = 0; b_ < 2; b_++)                                                \
       _Pragma("unroll") for (int h_ = 0; h_ < 2; h_++) {                                            \
         v2f m_[6], t_[4];                                                                           \
@@ -338,19 +299,17 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
           yo2[b_][h_][4 * a_ + 3] = __builtin_elementwise_fma(t_[a_], (v2f){c3, c3}, yo2[b_][h_][4 * a_ + 3]); \
         }                                                                                           \
       }                                                                                             \
-    if constexpr (!ZC) {                                                                              \
-      _Pragma("unroll") for (int x_ = 0; x_ < 6; x_++) acc[x_][0] = acc[x_][1] = (v4f){0.f, 0.f, 0.f, 0.f}; \
-    }                                                                                                 \
   }
 
   // One stage on accumulator set XI (XP = the set of the stage before when that was another plane):
   //   own DMAs of this stage landed (counted wait: the next stage's stay in flight) -> barrier
   //   (everybody's landed, everybody done reading the previous stage) -> DMA of stage s+2 into the
   //   buffer the previous stage just freed -> reads X(s) -> MFMAs Y(s-1) -> reads Y(s) -> MFMAs X(s)
+  // vmcnt(6): the 2 + WM_UB DMA instructions of the NEXT stage are what may still be in flight. (ABL_NO_BARRIER waits
+  // on a stricter vmcnt(4): every record of that ablation was measured with it.)
 #define WM_STAGE(XI, XP)                                                                              \
   do {                                                                                                \
-    if constexpr (ABL & 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                 \
-    else if constexpr (UB == 2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+    if constexpr (ABL & ABL_NO_BARRIER) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");   \
     else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");                     \
     WM_READ(xa0, xa1, xb, 0);                                                                         \
     __builtin_amdgcn_sched_barrier(0);   /* the X reads go out first: their latency hides under Y's MFMAs */ \
@@ -365,7 +324,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     __builtin_amdgcn_sched_barrier(0);                                                                \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   /* the X reads (issued 16 MFMAs ago) */        \
     __builtin_amdgcn_sched_barrier(0);                                                                \
-    if (ZC && kc == 0) { WM_MFMA1_Z(xa0, xa1, xb, 0, acc[XI]); }   /* a plane's first MFMAs: C = 0 */   \
+    if (kc == 0) { WM_MFMA1_Z(xa0, xa1, xb, 0, acc[XI]); }   /* a plane's first MFMAs: C = 0 */        \
     else { WM_MFMA1(xa0, xa1, xb, 0, acc[XI]); }                                                      \
     __builtin_amdgcn_sched_barrier(0);   /* the Y reads go out between X's MFMA groups: nothing waits for them before the next barrier */ \
     WM_READ(ya0, ya1, yb, 2);                                                                         \
@@ -375,7 +334,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   /* Y landed before the compiler may touch its registers (loop-carried) */ \
     cur = cur == 2 ? 0 : cur + 1;                                                                     \
   } while (0)
-  static_assert(WM_NBUF == 3, "WM_READ dispatches over a ring of three buffers");
+  static_assert(2 + WM_UB == 6, "the stage barrier's vmcnt(6) counts the 2 + WM_UB DMA instructions a wave issues per stage");
 
   // nu - 1 as a scalar loop variable of its own: written `nu - 1` next to the `nu > 0` test the compiler fuses the two into one
   // VECTOR subtract-with-borrow, whose result now outlives the X reads of the stage (one VGPR more than the kernel had)
@@ -411,7 +370,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
 #undef WM_DMA
 #undef WM_PF_ADVANCE
 
-  if constexpr (ABL & 256) {   // ablation: bias + ReLU on the registers, nothing staged or stored
+  if constexpr (ABL & ABL_EPI_REGS_ONLY) {
     const float bv_ = bv;
     float k_ = 0.f;
 #pragma unroll
@@ -423,7 +382,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     if (k_ == 12345.678f) y[tid] = k_;
     return;
   }
-  if constexpr (ABL & 32) {   // keep the accumulators alive, store one value per lane
+  if constexpr (ABL & ABL_NO_EPILOGUE) {
     float k_ = 0.f;
 #pragma unroll
     for (int b = 0; b < 2; b++)
@@ -436,66 +395,9 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     if (k_ == 12345.678f) y[tid] = k_;
     return;
   }
-  if constexpr (EPI == 1) {
-    // ---- epilogue, straight from registers (operand roles swapped: see EPI) ------------------------------------------------
-    // lane holds, per block b, tile 32 wm + 16 b + lr x channels 16 wn + 4 lk + i (i = 0..3): YO(b, i, 4 a + e)
-    static_assert(WR == 1 || !EPI, "the direct epilogue is written for 32-tile blocks");
-    const int HtWt = Ht * Wt;
-    const int bimg0 = (int)(t0 / HtWt);
-    const int rem0 = (int)(t0 - (long long)bimg0 * HtWt);
-    const int ty0 = rem0 / Wt, tx0 = rem0 - ty0 * Wt;
-    const int co4 = cb * WM_BC + 16 * wn + 4 * lk;
-    const int Hp = H / 2, Wp = W / 2;
-#pragma unroll
-    for (int b = 0; b < 2; b++) {
-      const int tl = 16 * b + lr;
-      const unsigned n = (unsigned)(tx0 + tl), q = n / (unsigned)Wt, tx = n - q * (unsigned)Wt;
-      const unsigned m = (unsigned)ty0 + q, q2 = m / (unsigned)Ht, ty = m - q2 * (unsigned)Ht;
-      const int img = bimg0 + (int)q2;
-      const bool mine = t0 + tl < tend;                      // (rows past the end of the group: computed on clamped operands, never stored)
-      v4f o[16];
-#pragma unroll
-      for (int px = 0; px < 16; px++) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          float val = YO(b, i, px) + bv4[i];
-          if (relu) val = val > 0.f ? val : 0.f;
-          o[px][i] = val;
-        }
-      }
-      if (POOL != 1) {
-        float* yb = y + (((long long)img * H + 4 * (int)ty) * W + 4 * (int)tx) * Cout + co4;
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-          for (int e = 0; e < 4; e++)
-            if (mine && 4 * (int)ty + a < H && 4 * (int)tx + e < W)
-              *reinterpret_cast<v4f*>(yb + ((long long)a * W + e) * Cout) = o[4 * a + e];
-      }
-      if (POOL != 0) {
-        float* yp = (POOL == 1 ? y : ypool) + (((long long)img * Hp + 2 * (int)ty) * Wp + 2 * (int)tx) * Cout + co4;
-#pragma unroll
-        for (int a2 = 0; a2 < 2; a2++)
-#pragma unroll
-          for (int e2 = 0; e2 < 2; e2++) {
-            v4f p = o[4 * (2 * a2) + 2 * e2];
-            const v4f p1 = o[4 * (2 * a2) + 2 * e2 + 1], p2 = o[4 * (2 * a2 + 1) + 2 * e2], p3 = o[4 * (2 * a2 + 1) + 2 * e2 + 1];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-              p[i] = p1[i] > p[i] ? p1[i] : p[i];
-              p[i] = p2[i] > p[i] ? p2[i] : p[i];
-              p[i] = p3[i] > p[i] ? p3[i] : p[i];
-            }
-            if (mine && 2 * (int)ty + a2 < Hp && 2 * (int)tx + e2 < Wp)
-              *reinterpret_cast<v4f*>(yp + ((long long)a2 * Wp + e2) * Cout) = p;
-          }
-      }
-    }
-    return;
-  }
   // ---- epilogue -------------------------------------------------------------------------------
-  // lane holds, per block b, tiles 32 wm + 16 b + 4 lk + i (i = 0..3) x channel 16 wn + lr
-  const int col = 16 * wn + lr;
+  // lane holds, per block b, tiles 16 b + 4 lk + i (i = 0..3) x channel 16 wave + lr
+  const int col = 16 * wave + lr;
 #pragma unroll
   for (int b = 0; b < 2; b++)
 #pragma unroll
@@ -507,13 +409,13 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
         YO(b, i, o) = val;
       }
 
-  // Staging through LDS: [BT tiles][4][64 channels] floats per pass, two buffers (the ring is free
+  // Staging through LDS: [WM_BT tiles][4][64 channels] floats per pass, two buffers (the ring is free
   // now) so that a pass needs ONE barrier: pass a+1 writes the buffer whose readers all arrived at
   // barrier a. Writer lanes (lr, lk) hit rows 4 lk tiles apart = the same banks, so the 16-channel
   // group is XORed with lk (reader: same XOR, wave-uniform, float4 alignment kept).
-  constexpr int SYF = BT * 4 * 64;
+  constexpr int SYF = WM_BT * 4 * 64;
   const int wcol = col ^ (16 * lk);
-  // The thread's 8 store slots: tile wave + NW r, pixel column re, channels rc4..rc4+3. Tile
+  // The thread's 8 store slots: tile wave + WM_NW r, pixel column re, channels rc4..rc4+3. Tile
   // coordinates by carries from the block's first tile (one 64-bit division per thread, not per store).
   const int HtWt = Ht * Wt;
   const int bimg0 = (int)(t0 / HtWt);
@@ -523,7 +425,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
   int s_img[8], s_tyx[8];   // image; ty | tx << 16 (ty = 0xffff: not this block's tile)
 #pragma unroll
   for (int r = 0; r < 8; r++) {
-    const int tl = wave + NW * r;
+    const int tl = wave + WM_NW * r;
     const unsigned n = (unsigned)(tx0 + tl), q = n / (unsigned)Wt, tx = n - q * (unsigned)Wt;
     const unsigned m = (unsigned)ty0 + q, q2 = m / (unsigned)Ht, ty = m - q2 * (unsigned)Ht;
     s_img[r] = bimg0 + (int)q2;
@@ -538,20 +440,20 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
       for (int b = 0; b < 2; b++)
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          const int tl = 32 * wm + 16 * b + 4 * lk + i;
+          const int tl = 16 * b + 4 * lk + i;
 #pragma unroll
           for (int e = 0; e < 4; e++) sY[(tl * 4 + e) * 64 + wcol] = YO(b, i, 4 * a + e);
         }
       __syncthreads();
 #pragma unroll
       for (int r = 0; r < 8; r++) {
-        const int tl = wave + NW * r;
+        const int tl = wave + WM_NW * r;
         const int ty = s_tyx[r] & 0xffff, tx = s_tyx[r] >> 16;
         const int oy = 4 * ty + a, ox = 4 * tx + re;
         if (oy < H && ox < W) {   // ty = 0xffff fails here
           const v4f o4 = *reinterpret_cast<const v4f*>(&sY[(tl * 4 + re) * 64 + (rc4 ^ (16 * ((tl >> 2) & 3)))]);
-          if constexpr (ABL & 128) { if (o4[0] == 12345.678f) y[tid] = o4[1]; }   // (ablation: the staged row is read, not stored)
-          else if constexpr (ABL & 512) __builtin_nontemporal_store(o4, reinterpret_cast<v4f*>(y + (((long long)s_img[r] * H + oy) * W + ox) * Cout + cb * WM_BC + rc4));
+          if constexpr (ABL & ABL_NO_STORES) { if (o4[0] == 12345.678f) y[tid] = o4[1]; }
+          else if constexpr (ABL & ABL_NT_STORES) __builtin_nontemporal_store(o4, reinterpret_cast<v4f*>(y + (((long long)s_img[r] * H + oy) * W + ox) * Cout + cb * WM_BC + rc4));
           else *reinterpret_cast<v4f*>(y + (((long long)s_img[r] * H + oy) * W + ox) * Cout + cb * WM_BC + rc4) = o4;
         }
       }
@@ -566,7 +468,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     for (int b = 0; b < 2; b++)
 #pragma unroll
       for (int i = 0; i < 4; i++) {
-        const int tl = 32 * wm + 16 * b + 4 * lk + i;
+        const int tl = 16 * b + 4 * lk + i;
 #pragma unroll
         for (int a2 = 0; a2 < 2; a2++)
 #pragma unroll
@@ -583,7 +485,7 @@ __global__ __launch_bounds__(256 * WR, 2) void wino43_mfma_kernel(
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-      const int tl = wave + NW * r;
+      const int tl = wave + WM_NW * r;
       const int ty = s_tyx[r] & 0xffff, tx = s_tyx[r] >> 16;
       const int py = 2 * ty + (re >> 1), px = 2 * tx + (re & 1);
       if (py < Hp && px < Wp)
@@ -666,7 +568,7 @@ extern "C" int pcnn_winograd43_conv_workspace_bytes(int B, int H, int W, int Cin
   PCNN_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cin >= 64 && Cout >= 64 && groups >= 1 && B % groups == 0, PCNN_EINVAL,
                "winograd43_conv_workspace_bytes: bad shape");
   const long long tpg = (long long)B * ((H + 3) / 4) * ((W + 3) / 4) / groups;
-  const int S = wino43_cin_split((long long)groups * ((tpg + 31) / 32), Cout / WM_BC, Cin);
+  const int S = wino43_cin_split((long long)groups * ((tpg + WM_BT - 1) / WM_BT), Cout / WM_BC, Cin);
   *bytes = S > 1 ? sizeof(float) * ((size_t)S * B * H * W * Cout + (size_t)groups * Cout) : 0;
   return PCNN_OK;
 }
@@ -692,10 +594,8 @@ extern "C" int pcnn_winograd43_conv_fwd(const float* v, const float* ut, const f
   const int ncb = Cout / WM_BC;
   // 32-tile blocks, two independent 4-wave workgroups per CU, for every layer: the pair drifts out of phase,
   // so one workgroup's barrier waits, column folds, epilogue stores and block turnover run under the other's
-  // MFMAs. Measured against 64-tile blocks (one 8-wave workgroup per CU, 2/3 of the operand bytes per flop,
-  // still instantiated by tools/wino_ablate.hip): conv3_2 1.87 -> 1.75 ms, conv3_1 1.02 -> 0.95, conv4_2
-  // 1.79 -> 1.78, 12-layer total 16.25 -> 15.86 ms.
-  const long long nbt = (long long)groups * ((tpg + 31) / 32);
+  // MFMAs (the numbers against 64-tile blocks, one 8-wave workgroup per CU, are at the kernel).
+  const long long nbt = (long long)groups * ((tpg + WM_BT - 1) / WM_BT);
   const long long blocks = ((nbt + 7) / 8) * 8 * ncb;
   PCNN_REQUIRE(blocks < (1ll << 31), PCNN_EINVAL, "winograd43_conv: grid too large");
   // the kernel addresses a plane of V and of U^T with 32-bit byte offsets from 64-bit plane bases
@@ -716,7 +616,7 @@ extern "C" int pcnn_winograd43_conv_fwd(const float* v, const float* ut, const f
   int mode = (ncb == 8 && u_bytes > v_bytes) ? 1 : 0;
   if (env_mode >= 0) mode = ((env_mode & 1) && ncb == 8) ? 1 : 0;
   const long long nblocks = (mode & 1) ? 8 * nbt : blocks;
-#define WM_GO(P, Y, BIAS, RELU, KS, STRIDE) PCNN_LAUNCH((wino43_mfma_kernel<P, 1, 0, 1>), dim3((unsigned)nblocks, KS), dim3(256), 0, stream, v, ut, BIAS, Y, y_pool, \
+#define WM_GO(P, Y, BIAS, RELU, KS, STRIDE) PCNN_LAUNCH((wino43_mfma_kernel<P>), dim3((unsigned)nblocks, KS), dim3(64 * WM_NW), 0, stream, v, ut, BIAS, Y, y_pool, \
                              H, W, Cin, Cout, Ht, Wt, T, tpg, RELU, (int)nbt, ncb, KS, (long long)(STRIDE), mode)
   if (S == 1) {
     if (pool == 0) WM_GO(0, y, bias, relu, 1, 0); else if (pool == 1) WM_GO(1, y, bias, relu, 1, 0); else WM_GO(2, y, bias, relu, 1, 0);

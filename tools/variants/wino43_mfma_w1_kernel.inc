@@ -1,7 +1,8 @@
 // tools/variants/wino43_mfma_w1_kernel.inc — the one-wave-per-SIMD trunk contraction of round 4 (DESIGN.md §3.2c), moved out of
 // libposecnn_hip.so in round 5 (VERDICT r4 #8): bit-identical to wino43_mfma_kernel, 3-10 % slower alone on every layer,
-// +0.8-1.3 % on the multi-stream step. Kept for tools/wino_w1_probe.hip, which #includes csrc/wino_mfma.hip first (constants,
-// glds16_s, at6_col live there) and checks the equality itself. Not compiled into the product library.
+// +0.8-1.3 % on the multi-stream step. Kept for tools/wino_w1_probe.hip, which #includes csrc/wino_mfma.hip first (the WM_*
+// constants live there; v4f and glds16_s come with it from csrc/mfma_ring.h) and checks the equality itself. Not compiled
+// into the product library. ("at6_col" below names the column transform t = A^T m of the library kernel's fold.)
 namespace {
 
 using namespace pcnn;

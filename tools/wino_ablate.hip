@@ -1,8 +1,9 @@
 // tools/wino_ablate.hip — "ablate before optimizing" (cdna_hip_programming.md §5.4): the fused Winograd
 // MFMA kernel of csrc/wino_mfma.hip with one ingredient of its K loop removed per variant, timed with HIP
-// events on synthetic buffers at a trunk layer's shape. Not part of the library. Build + run:
+// events on synthetic buffers at a trunk layer's shape (the ABL_* bits are documented at their enum in csrc/wino_mfma.hip).
+// Not part of the library. Build + run:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iposecnn_amd/csrc -Iinclude \
-//         tools/wino_ablate.hip posecnn_amd/csrc/common.hip -o tools/wino_ablate && tools/wino_ablate 9600 512 512
+//         tools/wino_ablate.hip posecnn_amd/csrc/common.hip -o tools/wino_ablate && tools/wino_ablate 32 60 80 512 512     (B H W Cin Cout)
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -10,20 +11,20 @@
 
 #include "../posecnn_amd/csrc/wino_mfma.hip"
 
-template <int ABL, int WR>
+template <int ABL>
 static float run(const float* v, const float* ut, const float* bias, float* y, int H, int W, int Cin, int Cout, long long T, int iters)
 {
   const int Ht = (H + 3) / 4, Wt = (W + 3) / 4;
-  const long long nbt = (T + 32 * WR - 1) / (32 * WR);
+  const long long nbt = (T + WM_BT - 1) / WM_BT;
   const int ncb = Cout / 64;
   const long long blocks = ((nbt + 7) / 8) * 8 * ncb;
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   for (int i = 0; i < 2; i++)
-    hipLaunchKernelGGL((wino43_mfma_kernel<0, WR, ABL>), dim3((unsigned)blocks), dim3(256 * WR), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
+    hipLaunchKernelGGL((wino43_mfma_kernel<0, ABL>), dim3((unsigned)blocks), dim3(64 * WM_NW), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
   hipEventRecord(e0, 0);
   for (int i = 0; i < iters; i++)
-    hipLaunchKernelGGL((wino43_mfma_kernel<0, WR, ABL>), dim3((unsigned)blocks), dim3(256 * WR), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
+    hipLaunchKernelGGL((wino43_mfma_kernel<0, ABL>), dim3((unsigned)blocks), dim3(64 * WM_NW), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
   hipEventRecord(e1, 0);
   hipEventSynchronize(e1);
   float ms = 0;
@@ -36,7 +37,6 @@ int main(int argc, char** argv)
   // image geometry: B images of H x W with T = B * (H/4) * (W/4) tiles
   const int B = argc > 1 ? atoi(argv[1]) : 32, H = argc > 2 ? atoi(argv[2]) : 60, W = argc > 3 ? atoi(argv[3]) : 80;
   const int Cin = argc > 4 ? atoi(argv[4]) : 512, Cout = argc > 5 ? atoi(argv[5]) : 512;
-  const int wr = argc > 6 ? atoi(argv[6]) : 2;
   const long long T = (long long)B * ((H + 3) / 4) * ((W + 3) / 4);
   float *v, *ut, *bias, *y;
   hipMalloc(&v, sizeof(float) * 36 * ((T + 63) / 64 * 64) * Cin);
@@ -50,27 +50,27 @@ int main(int argc, char** argv)
   hipMemcpy(bias, h.data(), sizeof(float) * Cout, hipMemcpyHostToDevice);
   const double fl = 2.0 * 36 * T * Cin * Cout;
   const int it = 10;
-#define R(ABL, WHAT) { float ms = wr == 2 ? run<ABL, 2>(v, ut, bias, y, H, W, Cin, Cout, T, it) : run<ABL, 1>(v, ut, bias, y, H, W, Cin, Cout, T, it); printf("%-44s %8.3f ms  %6.1f TFLOP/s-equivalent\n", WHAT, ms, fl / ms / 1e9); }
-  printf("T=%lld Cin=%d Cout=%d WR=%d\n", T, Cin, Cout, wr);
-  for (int w = 0; w < 250; w++) run<0, 1>(v, ut, bias, y, H, W, Cin, Cout, T, 5);   // clocks up (they ramp for seconds)
+#define R(ABL, WHAT) { float ms = run<ABL>(v, ut, bias, y, H, W, Cin, Cout, T, it); printf("%-44s %8.3f ms  %6.1f TFLOP/s-equivalent\n", WHAT, ms, fl / ms / 1e9); }
+  printf("T=%lld Cin=%d Cout=%d\n", T, Cin, Cout);
+  for (int w = 0; w < 250; w++) run<0>(v, ut, bias, y, H, W, Cin, Cout, T, 5);   // clocks up (they ramp for seconds)
   R(0, "full kernel");
-  R(64, "full kernel, every operand L2-resident");
+  R(ABL_L2_OPERANDS, "full kernel, every operand L2-resident");
   R(0, "full kernel (again)");
-  R(32, "no epilogue");
-  R(32 | 16, "no epilogue, no column fold");
-  R(32 | 1, "no epilogue, no barrier");
-  R(32 | 2, "no epilogue, no DMA");
-  R(32 | 4, "no epilogue, no LDS reads");
-  R(32 | 2 | 4, "no epilogue, no DMA, no LDS reads");
-  R(32 | 1 | 2 | 4 | 16, "MFMAs + loop control only");
-  R(32 | 8, "no epilogue, no MFMAs");
-  R(32 | 8 | 4, "no epilogue, no MFMAs, no LDS reads (DMA only)");
-  R(32 | 64, "no epilogue, every operand L2-resident");
-  R(512, "full kernel, non-temporal output stores");
+  R(ABL_NO_EPILOGUE, "no epilogue");
+  R(ABL_NO_EPILOGUE | ABL_NO_FOLD, "no epilogue, no column fold");
+  R(ABL_NO_EPILOGUE | ABL_NO_BARRIER, "no epilogue, no barrier");
+  R(ABL_NO_EPILOGUE | ABL_NO_DMA, "no epilogue, no DMA");
+  R(ABL_NO_EPILOGUE | ABL_NO_LDS_READS, "no epilogue, no LDS reads");
+  R(ABL_NO_EPILOGUE | ABL_NO_DMA | ABL_NO_LDS_READS, "no epilogue, no DMA, no LDS reads");
+  R(ABL_NO_EPILOGUE | ABL_NO_BARRIER | ABL_NO_DMA | ABL_NO_LDS_READS | ABL_NO_FOLD, "MFMAs + loop control only");
+  R(ABL_NO_EPILOGUE | ABL_NO_MFMA, "no epilogue, no MFMAs");
+  R(ABL_NO_EPILOGUE | ABL_NO_MFMA | ABL_NO_LDS_READS, "no epilogue, no MFMAs, no LDS reads (DMA only)");
+  R(ABL_NO_EPILOGUE | ABL_L2_OPERANDS, "no epilogue, every operand L2-resident");
+  R(ABL_NT_STORES, "full kernel, non-temporal output stores");
   R(0, "full kernel (again 3)");
-  R(512, "full kernel, non-temporal output stores (again)");
-  R(128, "epilogue without its global stores");
-  R(256, "epilogue = bias + ReLU only (no staging, no stores)");
+  R(ABL_NT_STORES, "full kernel, non-temporal output stores (again)");
+  R(ABL_NO_STORES, "epilogue without its global stores");
+  R(ABL_EPI_REGS_ONLY, "epilogue = bias + ReLU only (no staging, no stores)");
   R(0, "full kernel (again 2)");
   R(0, "full kernel (last)");
   return 0;

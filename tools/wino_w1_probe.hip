@@ -26,7 +26,7 @@ static float run_old(const float* v, const float* ut, const float* bias, float* 
   hipEventCreate(&e0); hipEventCreate(&e1);
   for (int i = 0; i < iters + 1; i++) {
     if (i == 1) hipEventRecord(e0, 0);
-    hipLaunchKernelGGL((wino43_mfma_kernel<POOL, 1, 0, 1>), dim3((unsigned)blocks, 1), dim3(256), 0, 0, v, ut, bias, y, yp, s.H, s.W, s.Cin,
+    hipLaunchKernelGGL((wino43_mfma_kernel<POOL>), dim3((unsigned)blocks, 1), dim3(256), 0, 0, v, ut, bias, y, yp, s.H, s.W, s.Cin,
                        s.Cout, Ht, Wt, T, tpg, 1, (int)nbt, ncb, 1, 0ll, 0);
   }
   hipEventRecord(e1, 0);
