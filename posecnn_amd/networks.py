@@ -390,6 +390,7 @@ class Network(object):
                         if pname == "weights" and t.dim() == 4 and op_name.startswith("upscore") and hasattr(self, "fused_heads"):
                             # a trained / non-bilinear deconv filter: conv1x1 and deconv no longer commute
                             self.fused_heads = False
+                            self.lowres_train_heads = False
         live = set(map(id, self.vars.values()))   # what was derived from a variable that has left `vars` goes with it
         self._cache = {slot: e for slot, e in self._cache.items() if live.issuperset(map(id, e[0]))}
 
@@ -800,7 +801,7 @@ class vgg16_convs(Network):
     def __init__(self, input_format, num_classes, num_units, scales, threshold_label, vote_threshold,
                  vertex_reg_2d=False, vertex_reg_3d=False, pose_reg=False, adaptation=False, trainable=True,
                  is_train=True, device="cuda", seed=3, init="he", with_losses=None, fused_heads=True,
-                 want_prob=True, fused_pool=True, strict_numerics=False):
+                 want_prob=True, fused_pool=True, strict_numerics=False, lowres_train_heads=False):
         Network.__init__(self, device=device, seed=seed, init=init, trainable=trainable)
         # strict_numerics: every 3x3 layer as a direct f32 convolution (library kernels) instead of Winograd
         # F(4x4,3x3). Both are exact in real arithmetic and f32 throughout; they differ in summation order
@@ -825,6 +826,12 @@ class vgg16_convs(Network):
         # identical low-resolution form + fused gfx950 epilogue (see setup()).
         # (the fused epilogues have no backward: a trainable training graph keeps the literal order)
         self.fused_heads = fused_heads and not (is_train and trainable)
+        # lowres_train_heads (opt-in, trainable training graphs only): the training twin of the fused heads. The `score` and
+        # `vertex_pred` contractions run at 1/8 resolution under autograd; the label head ends in ops.label_head_loss
+        # (deconv + bias + ReLU + softmax + argmax + Hardlabel + cross entropy in one kernel, with a backward), the vertex
+        # head in the differentiable ops.deconv_bilinear. Same variables, same names; `upscore`, `score`, `prob`,
+        # `prob_normalized`, `gt_label_weight` and `upscore_vertex` are not built.
+        self.lowres_train_heads = bool(lowres_train_heads and is_train and trainable)
         self.want_prob = want_prob  # prob_normalized is a fetched output in lib/fcn/test.py:193-195
         self.input_format = input_format
         self.num_classes = num_classes
@@ -859,10 +866,18 @@ class vgg16_convs(Network):
         self.setup()
         return self
 
-    def _conv1x1_lowres(self, x, name, c_o, c_i):
+    LOWRES_TRAIN_ABSENT = ('upscore', 'score', 'prob', 'prob_normalized', 'gt_label_weight', 'upscore_vertex')
+
+    def get_output(self, name):
+        if self.lowres_train_heads and name in self.LOWRES_TRAIN_ABSENT and name not in self.layers:
+            raise KeyError("layer %s is not built with lowres_train_heads=True: the label head leaves ops.label_head_loss as "
+                           "`loss_cls` and `label_2d` (build the graph with lowres_train_heads=False to fetch it)" % name)
+        return Network.get_output(self, name)
+
+    def _conv1x1_lowres(self, x, name, c_o, c_i, trainable=False):
         """The 1x1 conv `name` (same variables as Network.conv would create) applied WITHOUT bias
         or ReLU; returns (z, bias) for the fused deconv epilogue."""
-        w, b = self._conv_vars(name, c_o, c_i, 1, 1, False)
+        w, b = self._conv_vars(name, c_o, c_i, 1, 1, trainable)
         return _nhwc(F.conv2d(_nchw(x), w, None)), b
 
     def _head_conv1x1(self, sources, c_o, name, relu=True):
@@ -1157,7 +1172,15 @@ class vgg16_convs(Network):
                  ._plant('add_score', 'add_score')
                  .dropout(self.keep_prob_queue, name='dropout'))
 
-        if self.fused_heads:
+        if self.lowres_train_heads:
+            # the commutation of the fused heads below, under autograd: the 64 -> C contraction at 1/8 resolution goes through
+            # the framework, everything after it is one kernel each way (csrc/label_loss.hip)
+            z, b = self._conv1x1_lowres(self.get_output('dropout'), 'score', self.num_classes, self.num_units, trainable=True)
+            loss_cls, label = ops.label_head_loss(z, b, self.get_output('gt_label_2d'), self.threshold_label,
+                                                  int(16 * self.scale), int(8 * self.scale), relu=True)
+            self.layers['loss_cls'] = loss_cls
+            self.layers['label_2d'] = label
+        elif self.fused_heads:
             # deconv and the 1x1 `score` conv are both linear and act on different axes, so
             # conv1x1(deconv(x)) + b == deconv(conv1x1(x)) + b exactly in real arithmetic (borders
             # included): run the 64->C contraction at 1/8 resolution (64x fewer MACs) and let one
@@ -1192,7 +1215,7 @@ class vgg16_convs(Network):
                  .softmax_high_dimension(self.num_classes, name='prob_normalized')
                  .argmax_2d(name='label_2d'))
 
-        if self.with_losses and 'gt_label_weight' not in self.layers:   # (else: it left the label head's launch)
+        if self.with_losses and not self.lowres_train_heads and 'gt_label_weight' not in self.layers:   # (else: it left the label head's launch)
             (self.feed('prob_normalized', 'gt_label_2d')
                  .hard_label(threshold=self.threshold_label, name='gt_label_weight'))
 
@@ -1210,7 +1233,13 @@ class vgg16_convs(Network):
                      .add(name='add_score_vertex')
                      ._plant('add_score_vertex', 'add_score_vertex')
                      .dropout(self.keep_prob_queue, name='dropout_vertex'))
-            if self.fused_heads:
+            if self.lowres_train_heads:
+                # 128 -> 3C at 1/8 resolution under autograd, then the differentiable interpolation: `upscore_vertex` and the
+                # full-resolution contraction are gone, vertex_pred itself is read by the vertex loss and the Hough layer
+                zv, bv = self._conv1x1_lowres(self.get_output('dropout_vertex'), 'vertex_pred', 3 * self.num_classes, 128,
+                                              trainable=True)
+                self.layers['vertex_pred'] = self._deconv_bilinear(zv, int(16 * self.scale), int(8 * self.scale), bias=bv)
+            elif self.fused_heads:
                 # same commutation as the label head: 128->3C at 1/8 resolution, then one
                 # interpolation pass writes vertex_pred (+ bias); `upscore_vertex` is never built
                 # and the Hough layer interpolates just the pixels it samples, so `vertex_pred`

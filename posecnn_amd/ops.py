@@ -24,6 +24,7 @@ __all__ = [
     "hough_voting_grad", "hard_label_grad", "hough_rows_capacity",
     "upscore_softmax_argmax", "Workspace", "vertex_targets", "smooth_l1_loss_vertex_gt",
     "depth_normals", "bilateral_filter_u8", "normal_image", "bilateral_tables", "augment_frames",
+    "label_head_loss", "label_head_loss_grad",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1019,6 +1020,95 @@ def upscore_softmax_argmax(z, bias, kernel, stride, relu=True, want_score=False,
           lib().pcnn_upscore_softmax_argmax_fwd(_ptr(z), _ptr(bias), B, H, W, C, int(kernel), int(stride),
                                                 1 if relu else 0, _ptr(score), _ptr(prob), _ptr(label), _stream(z)))
     return score, prob, label
+
+
+def _label_head_loss_args(z, bias, gt_label_2d, kernel, stride):
+    z = _dev(z, "z", torch.float32)
+    bias = _dev(bias, "bias", torch.float32)
+    gt = _dev(gt_label_2d, "gt_label_2d", torch.int32)
+    if z.dim() != 4 or bias.dim() != 1 or bias.shape[0] != z.shape[3]:
+        raise ValueError("z must be [B,H,W,C] and bias [C] (got %s, %s)" % (tuple(z.shape), tuple(bias.shape)))
+    B, H, W, C = z.shape
+    if tuple(gt.shape) != (B, H * stride, W * stride):
+        raise ValueError("gt_label_2d must be int32 [B, H*stride, W*stride] = %s (got %s)"
+                         % ((B, H * stride, W * stride), tuple(gt.shape)))
+    nbytes = c_size_t(0)
+    check("pcnn_label_head_loss_workspace_bytes",
+          lib().pcnn_label_head_loss_workspace_bytes(B, H, W, C, int(kernel), int(stride), ctypes.byref(nbytes)))
+    ws = _ws(z.device, "label_head_loss").get(nbytes.value, z.device)
+    return z, bias, gt, ws
+
+
+def _label_head_loss_raw(z, bias, gt_label_2d, threshold, kernel, stride, relu=True, want_terms=False):
+    """-> (loss f32 [], sums f64 [2] = (S, count), label_2d int32 [B,Ho,Wo], terms f32 [B,Ho,Wo] | None): one call of
+    pcnn_label_head_loss_fwd (include/posecnn_hip_loss.h)."""
+    z, bias, gt, ws = _label_head_loss_args(z, bias, gt_label_2d, kernel, stride)
+    B, H, W, C = z.shape
+    dev = z.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    label = torch.empty(gt.shape, dtype=torch.int32, device=dev)
+    terms = torch.empty(gt.shape, dtype=torch.float32, device=dev) if want_terms else None
+    check("pcnn_label_head_loss_fwd",
+          lib().pcnn_label_head_loss_fwd(_ptr(z), _ptr(bias), _ptr(gt), B, H, W, C, int(kernel), int(stride), 1 if relu else 0,
+                                         float(threshold), _ptr(loss), _ptr(sums), _ptr(label), _ptr(terms), _ptr(ws),
+                                         ws.numel(), _stream(z)))
+    return loss, sums, label, terms
+
+
+def label_head_loss_grad(z, bias, gt_label_2d, threshold, kernel, stride, relu=True, upstream=None, sums=None):
+    """The backward kernel of `label_head_loss` on its own: -> (dscore f32 [B,H*s,W*s,C], dbias f32 [C]), the gradient of
+    upstream * loss w.r.t. the full-resolution score and the bias; `deconv_bilinear_grad(dscore, kernel, stride)` is the
+    one w.r.t. z. `upstream` is a one-element f32 tensor on the device (None: 1), `sums` what the forward saved (None: the
+    forward is run for it)."""
+    if sums is None:
+        sums = _label_head_loss_raw(z, bias, gt_label_2d, threshold, kernel, stride, relu)[1]
+    z, bias, gt, ws = _label_head_loss_args(z, bias, gt_label_2d, kernel, stride)
+    sums = _dev(sums, "sums", torch.float64)
+    up = _dev(upstream, "upstream", torch.float32).reshape(1) if upstream is not None else None
+    B, H, W, C = z.shape
+    dscore = torch.empty(tuple(gt.shape) + (C,), dtype=torch.float32, device=z.device)
+    dbias = torch.empty(C, dtype=torch.float32, device=z.device)
+    check("pcnn_label_head_loss_bwd",
+          lib().pcnn_label_head_loss_bwd(_ptr(z), _ptr(bias), _ptr(gt), _ptr(sums), _ptr(up), B, H, W, C, int(kernel),
+                                         int(stride), 1 if relu else 0, float(threshold), _ptr(dscore), _ptr(dbias), _ptr(ws),
+                                         ws.numel(), _stream(z)))
+    return dscore, dbias
+
+
+class _LabelHeadLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, bias, gt, threshold, kernel, stride, relu, want_terms):
+        loss, sums, label, terms = _label_head_loss_raw(z, bias, gt, threshold, kernel, stride, relu, want_terms)
+        ctx.save_for_backward(z, bias, gt, sums)
+        ctx.cfg = (threshold, kernel, stride, relu)
+        ctx.mark_non_differentiable(label)
+        if terms is None:
+            return loss, label
+        ctx.mark_non_differentiable(terms)
+        return loss, label, terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, *_unused):
+        z, bias, gt, sums = ctx.saved_tensors
+        threshold, kernel, stride, relu = ctx.cfg
+        up = grad_loss.reshape(1).to(torch.float32).contiguous()
+        dscore, dbias = label_head_loss_grad(z, bias, gt, threshold, kernel, stride, relu, upstream=up, sums=sums)
+        dz = deconv_bilinear_grad(dscore, kernel, stride)
+        return dz, dbias, None, None, None, None, None, None
+
+
+def label_head_loss(z, bias, gt_label_2d, threshold, kernel, stride, relu=True, want_terms=False):
+    """The label head of the training graph in one pass from the 1/8-resolution class scores z [B,H,W,C] (without bias):
+    score = [ReLU](deconv(z) + bias) -> softmax -> first argmax, the Hardlabel rule on (prob, gt_label_2d, threshold) and
+    loss_cross_entropy_single_frame (lib/fcn/train.py:41-44) over its weights, without a [B,H*s,W*s,C] tensor.
+    Returns (loss f32 [], label_2d int32 [B,H*s,W*s]) and, with `want_terms`, the per-pixel terms f32 [B,H*s,W*s].
+    Differentiable w.r.t. z and bias; no gradient flows through the Hardlabel rule or the argmax, as the reference
+    registers them (hard_label_op_gpu.cu.cc:55-63)."""
+    z = _dev(z, "z", torch.float32)
+    bias = _dev(bias, "bias", torch.float32)
+    gt = _dev(gt_label_2d, "gt_label_2d", torch.int32)
+    return _LabelHeadLossFn.apply(z, bias, gt, float(threshold), int(kernel), int(stride), bool(relu), bool(want_terms))
 
 
 # ------------------------------------------------------------------------------------------------

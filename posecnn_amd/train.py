@@ -7,7 +7,8 @@ The custom layers bring their own gradients (ROI pooling, average-distance loss,
 zeros for Hough voting and hard labels, as the reference registers them); the fixed bilinear
 deconvs and the vertex loss have hand-written gfx950 backward kernels; convolutions / fc layers go
 through the framework's autograd. A trainable `vgg16_convs(is_train=True)` evaluates the heads in
-the reference's literal op order (the fused inference epilogues have no backward).
+the reference's literal op order (the fused inference epilogues have no backward) unless it is built with
+`lowres_train_heads=True`: then the label head is `ops.label_head_loss`, which has one.
 """
 import torch
 
@@ -81,7 +82,10 @@ def build_losses(net, cfg=TrainConfig):
     (and, for multi-instance frames, `vertex_instance`) instead of `vertex_targets` / `vertex_weights` takes the
     target-free vertex loss."""
     out = {}
-    out["loss_cls"] = loss_cross_entropy_single_frame(net.get_output("prob"), net.get_output("gt_label_weight"))
+    if "loss_cls" in net.layers:    # vgg16_convs(lowres_train_heads=True): the loss left the label head's own kernel
+        out["loss_cls"] = net.get_output("loss_cls")
+    else:
+        out["loss_cls"] = loss_cross_entropy_single_frame(net.get_output("prob"), net.get_output("gt_label_weight"))
     out["loss_regu"] = regularization_loss(net, cfg.WEIGHT_REG)
     loss = out["loss_cls"] + out["loss_regu"]
     if net.vertex_reg:
