@@ -4,7 +4,7 @@
 // of at most 64 objects per frame; only 3 of a foreground pixel's 3C channels carry weight.
 //
 //   vt_tile_kernel<VT_TARGETS>   writes targets + weights        (the generator: API completeness, the yardstick)
-//   sl1_gt_partial_kernel        loss forward without them       (+ sl1_final_kernel of sl1_device.h)
+//   sl1_gt_partial_kernel        loss forward without them       (sl1_gt_device.h; + sl1_final_kernel of sl1_device.h)
 //   vt_tile_kernel<VT_GRAD>      loss backward without them      (writes the full grad_pred)
 //
 // Arithmetic of a matched pixel: include/posecnn_hip_train.h. Float64, one rounding per operation (-ffp-contract=off;
@@ -20,7 +20,7 @@
 // and a + (+0) == a bitwise for every value the accumulators can hold (they start at +0 and never become -0), so
 // skipping it changes nothing: pred is loaded only under a matching row. Precondition: pred finite where the weight
 // is 0 (the unfused kernel would make 0 * inf = NaN of it).
-#include "sl1_device.h"
+#include "sl1_gt_device.h"
 
 #include "../../include/posecnn_hip_train.h"
 
@@ -29,29 +29,6 @@ namespace {
 constexpr int VT_MAX_OBJECTS = 64;
 constexpr int VT_TILE = 256;       // pixels per block = threads per block
 constexpr int VT_TARGETS = 0, VT_GRAD = 1;
-constexpr int SL1_GT_UNROLL = 8;   // labels in flight per thread (4 waves per SIMD: the loads need the ILP)
-
-// The highest-index row of `tab` ([M,6]: cls, mask_id, cx, cy, log_z, w) that matches label l / instance inst at
-// pixel (x, y) -> its targets and weight. No early exit: the M row reads are independent of each other.
-__device__ __forceinline__ bool vt_match(const float* tab, int M, int l, int inst, int x, int y, float& tx,
-                                         float& ty, float& tz, float& w)
-{
-  const float lf = (float)l, instf = (float)inst;
-  int sel = -1;
-  for (int j = 0; j < M; ++j) {
-    const float cls = tab[6 * j], mid = tab[6 * j + 1];
-    if (cls == lf && (mid == 0.f || mid == instf)) sel = j;
-  }
-  if (sel < 0) return false;
-  const double dx = (double)tab[6 * sel + 2] - (double)x;
-  const double dy = (double)tab[6 * sel + 3] - (double)y;
-  const double n = __builtin_sqrt(dx * dx + dy * dy) + 1e-10;
-  tx = (float)(dx / n);
-  ty = (float)(dy / n);
-  tz = tab[6 * sel + 4];
-  w = tab[6 * sel + 5];
-  return true;
-}
 
 // element `ch` of tile pixel `pix`: its pixel's value if ch is one of the three live channels, else +0
 template <int MODE>
@@ -167,68 +144,6 @@ __global__ __launch_bounds__(VT_TILE) void vt_tile_kernel(const int32_t* __restr
   }
 }
 
-// qs / rs: quotient and remainder of the element stride SL1_BLOCKS * 256 by 3C.
-__global__ __launch_bounds__(256) void sl1_gt_partial_kernel(const float* __restrict__ pred,
-                                                             const int32_t* __restrict__ label,
-                                                             const int32_t* __restrict__ instance,
-                                                             const float* __restrict__ objects, long long n,
-                                                             int HW, int W, int C, int M, float sigma2, int qs,
-                                                             int rs, float* __restrict__ partial)
-{
-  __shared__ float sl[256], sw[256];
-  const int t = threadIdx.x;
-  const int C3 = 3 * C;
-  constexpr long long STRIDE = (long long)SL1_BLOCKS * 256;
-  float al = 0.f, aw = 0.f;
-  int pix = (blockIdx.x * 256 + t) / C3, ch = (blockIdx.x * 256 + t) - pix * C3;
-  for (long long i = (long long)blockIdx.x * 256 + t; i < n; i += STRIDE * SL1_GT_UNROLL) {
-    int lab[SL1_GT_UNROLL], px[SL1_GT_UNROLL], cc[SL1_GT_UNROLL];
-#pragma unroll
-    for (int k = 0; k < SL1_GT_UNROLL; ++k) {
-      px[k] = pix;
-      cc[k] = ch;
-      lab[k] = i + k * STRIDE < n ? label[pix] : 0;   // past the end: background, adds nothing
-      pix += qs;
-      ch += rs;
-      if (ch >= C3) {
-        ch -= C3;
-        ++pix;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < SL1_GT_UNROLL; ++k) {   // m ascending: the accumulation order of sl1_partial_kernel
-      const int l = lab[k];
-      const int d = cc[k] - 3 * l;
-      if (l > 0 && l < C && (unsigned)d < 3u) {
-        const int f = px[k] / HW, rem = px[k] - f * HW;
-        const int y = rem / W, x = rem - y * W;
-        const int inst = instance ? instance[px[k]] : 0;
-        float tx, ty, tz, w;
-        if (vt_match(objects + (long long)f * M * 6, M, l, inst, x, y, tx, ty, tz, w)) {
-          float il, dp;
-          sl1_elem(pred[i + k * STRIDE], d == 0 ? tx : (d == 1 ? ty : tz), w, sigma2, il, dp);
-          al = al + il;
-          aw = aw + w;
-        }
-      }
-    }
-  }
-  sl[t] = al;
-  sw[t] = aw;
-  __syncthreads();
-  for (int st = 128; st >= 1; st >>= 1) {
-    if (t < st) {
-      sl[t] = sl[t] + sl[t + st];
-      sw[t] = sw[t] + sw[t + st];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    partial[blockIdx.x] = sl[0];
-    partial[SL1_BLOCKS + blockIdx.x] = sw[0];
-  }
-}
-
 // shape checks shared by the three entries; *pixels = B*H*W
 int vt_check_shape(const char* who, int B, int H, int W, int C, int M, long long* pixels)
 {
@@ -273,8 +188,8 @@ extern "C" int pcnn_smooth_l1_vertex_gt_fwd(const float* pred, const int32_t* la
   hipStream_t stream = (hipStream_t)stream_;
   float* partial = (float*)workspace;
   const int C3 = 3 * C, stride = SL1_BLOCKS * 256;
-  PCNN_LAUNCH(sl1_gt_partial_kernel, dim3(SL1_BLOCKS), dim3(256), 0, stream, pred, label, instance, objects,
-              pixels * C3, H * W, W, C, M, sigma * sigma, stride / C3, stride % C3, partial);
+  PCNN_LAUNCH(sl1_gt_partial_kernel<PredTensor>, dim3(SL1_BLOCKS), dim3(256), 0, stream, PredTensor{pred}, label, instance,
+              objects, pixels * C3, H * W, W, C, M, sigma * sigma, stride / C3, stride % C3, partial);
   PCNN_LAUNCH(sl1_final_kernel, dim3(1), dim3(SL1_BLOCKS / 2), 0, stream, partial, out);
   return check_launch("smooth_l1_vertex_gt_fwd");
 }

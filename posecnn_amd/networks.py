@@ -801,7 +801,7 @@ class vgg16_convs(Network):
     def __init__(self, input_format, num_classes, num_units, scales, threshold_label, vote_threshold,
                  vertex_reg_2d=False, vertex_reg_3d=False, pose_reg=False, adaptation=False, trainable=True,
                  is_train=True, device="cuda", seed=3, init="he", with_losses=None, fused_heads=True,
-                 want_prob=True, fused_pool=True, strict_numerics=False, lowres_train_heads=False):
+                 want_prob=True, fused_pool=True, strict_numerics=False, lowres_train_heads=False, fused_vertex_loss=False):
         Network.__init__(self, device=device, seed=seed, init=init, trainable=trainable)
         # strict_numerics: every 3x3 layer as a direct f32 convolution (library kernels) instead of Winograd
         # F(4x4,3x3). Both are exact in real arithmetic and f32 throughout; they differ in summation order
@@ -832,6 +832,11 @@ class vgg16_convs(Network):
         # head in the differentiable ops.deconv_bilinear. Same variables, same names; `upscore`, `score`, `prob`,
         # `prob_normalized`, `gt_label_weight` and `upscore_vertex` are not built.
         self.lowres_train_heads = bool(lowres_train_heads and is_train and trainable)
+        # fused_vertex_loss (opt-in, on top of lowres_train_heads): when the feed carries `vertex_objects` and no dense
+        # `vertex_targets`, the vertex head ends in ops.vertex_head_loss (interpolation + bias + target-free smooth-L1 in one
+        # kernel each way, csrc/vertex_head_loss.hip) as `loss_vertex_sl1`, the Hough layer reads the 1/8-resolution field as
+        # in inference, and `vertex_pred` is only built if somebody fetches it. Any other feed builds today's graph.
+        self.fused_vertex_loss = bool(fused_vertex_loss and self.lowres_train_heads)
         self.want_prob = want_prob  # prob_normalized is a fetched output in lib/fcn/test.py:193-195
         self.input_format = input_format
         self.num_classes = num_classes
@@ -1233,12 +1238,26 @@ class vgg16_convs(Network):
                      .add(name='add_score_vertex')
                      ._plant('add_score_vertex', 'add_score_vertex')
                      .dropout(self.keep_prob_queue, name='dropout_vertex'))
+            lowres_hough = False
             if self.lowres_train_heads:
                 # 128 -> 3C at 1/8 resolution under autograd, then the differentiable interpolation: `upscore_vertex` and the
                 # full-resolution contraction are gone, vertex_pred itself is read by the vertex loss and the Hough layer
                 zv, bv = self._conv1x1_lowres(self.get_output('dropout_vertex'), 'vertex_pred', 3 * self.num_classes, 128,
                                               trainable=True)
-                self.layers['vertex_pred'] = self._deconv_bilinear(zv, int(16 * self.scale), int(8 * self.scale), bias=bv)
+                # (the fused loss needs the object-table feed; with dense targets the head stays as it was)
+                lowres_hough = (self.fused_vertex_loss and 'vertex_objects' in self.layers
+                                and 'vertex_targets' not in self.layers)
+                if lowres_hough:
+                    kv, sv = int(16 * self.scale), int(8 * self.scale)
+                    instance = self.get_output('vertex_instance') if 'vertex_instance' in self.layers else None
+                    self.layers['loss_vertex_sl1'] = ops.vertex_head_loss(zv, bv, self.get_output('gt_label_2d'),
+                                                                          self.get_output('vertex_objects'), kv, sv, instance)[0]
+                    zd, bd = zv.detach(), bv.detach()
+                    self.layers['vertex_pred_lowres'] = zd
+                    self.layers['vertex_pred_bias'] = bd
+                    self.layers['vertex_pred'] = _Lazy(lambda: self._deconv_bilinear(zd, kv, sv, bias=bd))
+                else:
+                    self.layers['vertex_pred'] = self._deconv_bilinear(zv, int(16 * self.scale), int(8 * self.scale), bias=bv)
             elif self.fused_heads:
                 # same commutation as the label head: 128->3C at 1/8 resolution, then one
                 # interpolation pass writes vertex_pred (+ bias); `upscore_vertex` is never built
@@ -1255,7 +1274,7 @@ class vgg16_convs(Network):
                      .conv(1, 1, 3 * self.num_classes, 1, 1, name='vertex_pred', relu=False, c_i=128))
 
             if self.vertex_reg_2d:
-                if self.fused_heads:
+                if self.fused_heads or lowres_hough:
                     (self.feed('label_2d', 'vertex_pred_lowres', 'vertex_pred_bias', 'extents', 'meta_data', 'poses')
                          .hough_voting_gpu_lowres(kv, sv, self.is_train, self.vote_threshold, self.vote_percentage,
                                                   self.skip_pixels, name='hough'))

@@ -24,7 +24,7 @@ __all__ = [
     "hough_voting_grad", "hard_label_grad", "hough_rows_capacity",
     "upscore_softmax_argmax", "Workspace", "vertex_targets", "smooth_l1_loss_vertex_gt",
     "depth_normals", "bilateral_filter_u8", "normal_image", "bilateral_tables", "augment_frames",
-    "label_head_loss", "label_head_loss_grad",
+    "label_head_loss", "label_head_loss_grad", "vertex_head_loss", "vertex_head_loss_grad",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1109,6 +1109,82 @@ def label_head_loss(z, bias, gt_label_2d, threshold, kernel, stride, relu=True, 
     bias = _dev(bias, "bias", torch.float32)
     gt = _dev(gt_label_2d, "gt_label_2d", torch.int32)
     return _LabelHeadLossFn.apply(z, bias, gt, float(threshold), int(kernel), int(stride), bool(relu), bool(want_terms))
+
+
+def _vertex_head_loss_args(z, bias, gt_label_2d, objects, instance, kernel, stride):
+    z = _dev(z, "z", torch.float32)
+    bias = _dev(bias, "bias", torch.float32)
+    label, obj, instance = _vertex_gt_args(gt_label_2d, objects, instance)
+    if z.dim() != 4 or z.shape[3] % VERTEX_CHANNELS or bias.dim() != 1 or bias.shape[0] != z.shape[3]:
+        raise ValueError("z must be [B,H,W,3C] and bias [3C] (got %s, %s)" % (tuple(z.shape), tuple(bias.shape)))
+    B, H, W, C3 = z.shape
+    if tuple(label.shape) != (B, H * stride, W * stride):
+        raise ValueError("gt_label_2d must be int32 [B, H*stride, W*stride] = %s (got %s)"
+                         % ((B, H * stride, W * stride), tuple(label.shape)))
+    nbytes = c_size_t(0)
+    check("pcnn_vertex_head_loss_workspace_bytes",
+          lib().pcnn_vertex_head_loss_workspace_bytes(B, H, W, C3 // VERTEX_CHANNELS, int(kernel), int(stride),
+                                                      ctypes.byref(nbytes)))
+    ws = _ws(z.device, "vertex_head_loss").get(nbytes.value, z.device)
+    return z, bias, label, obj, instance, ws
+
+
+def _vertex_head_loss_raw(z, bias, gt_label_2d, objects, kernel, stride, instance=None, sigma=1.0):
+    """-> out f32 [3] = (loss, sum(in_loss), sum(w)): one call of pcnn_vertex_head_loss_fwd (include/posecnn_hip_vertex_loss.h)."""
+    z, bias, label, obj, instance, ws = _vertex_head_loss_args(z, bias, gt_label_2d, objects, instance, kernel, stride)
+    B, H, W, C3 = z.shape
+    out = torch.empty(3, dtype=torch.float32, device=z.device)
+    check("pcnn_vertex_head_loss_fwd",
+          lib().pcnn_vertex_head_loss_fwd(_ptr(z), _ptr(bias), _ptr(label), _ptr(instance), _ptr(obj), B, H, W,
+                                          C3 // VERTEX_CHANNELS, obj.shape[1], int(kernel), int(stride), float(sigma), _ptr(out),
+                                          _ptr(ws), ws.numel(), _stream(z)))
+    return out
+
+
+def vertex_head_loss_grad(z, bias, gt_label_2d, objects, kernel, stride, instance=None, sigma=1.0, upstream=None, out=None):
+    """The backward kernel of `vertex_head_loss` on its own: -> (dz f32 [B,H,W,3C], dbias f32 [3C]), the gradient of
+    upstream * loss w.r.t. the low-resolution field and the bias. `upstream` is a one-element f32 tensor on the device
+    (None: 1), `out` the three floats the forward saved (None: the forward is run for them)."""
+    if out is None:
+        out = _vertex_head_loss_raw(z, bias, gt_label_2d, objects, kernel, stride, instance, sigma)
+    z, bias, label, obj, instance, ws = _vertex_head_loss_args(z, bias, gt_label_2d, objects, instance, kernel, stride)
+    out = _dev(out, "out", torch.float32)
+    up = _dev(upstream, "upstream", torch.float32).reshape(1) if upstream is not None else None
+    B, H, W, C3 = z.shape
+    dz = torch.empty_like(z)
+    dbias = torch.empty(C3, dtype=torch.float32, device=z.device)
+    check("pcnn_vertex_head_loss_bwd",
+          lib().pcnn_vertex_head_loss_bwd(_ptr(z), _ptr(bias), _ptr(label), _ptr(instance), _ptr(obj), _ptr(out), _ptr(up), B, H,
+                                          W, C3 // VERTEX_CHANNELS, obj.shape[1], int(kernel), int(stride), float(sigma),
+                                          _ptr(dz), _ptr(dbias), _ptr(ws), ws.numel(), _stream(z)))
+    return dz, dbias
+
+
+class _VertexHeadLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, bias, label, obj, instance, kernel, stride, sigma):
+        out = _vertex_head_loss_raw(z, bias, label, obj, kernel, stride, instance, sigma)
+        ctx.save_for_backward(z, bias, label, obj, out, instance)
+        ctx.cfg = (kernel, stride, sigma)
+        return out[0], out[1:].clone()
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_sums):
+        z, bias, label, obj, out, instance = ctx.saved_tensors
+        kernel, stride, sigma = ctx.cfg
+        up = grad_loss.reshape(1).to(torch.float32).contiguous()
+        dz, dbias = vertex_head_loss_grad(z, bias, label, obj, kernel, stride, instance, sigma, upstream=up, out=out)
+        return dz, dbias, None, None, None, None, None, None
+
+
+def vertex_head_loss(z, bias, gt_label_2d, objects, kernel, stride, instance=None, sigma=1.0):
+    """The vertex head of the training graph from the 1/stride-resolution field z [B,H,W,3C] (without bias):
+    `smooth_l1_loss_vertex_gt(deconv_bilinear(z, kernel, stride) + bias, gt_label_2d, objects, instance, sigma)` — the same
+    bits, loss and gradient w.r.t. z — without vertex_pred [B,H*s,W*s,3C] or its gradient ever being written: the
+    interpolation runs only under a matching row, for the three channels that carry weight. Returns (loss f32 [],
+    sums f32 [2] = (sum(in_loss), sum(w))). Differentiable w.r.t. z and bias; z and bias must be finite."""
+    z, bias, label, obj, instance, _ = _vertex_head_loss_args(z, bias, gt_label_2d, objects, instance, kernel, stride)
+    return _VertexHeadLossFn.apply(z, bias, label, obj, instance, int(kernel), int(stride), float(sigma))
 
 
 # ------------------------------------------------------------------------------------------------

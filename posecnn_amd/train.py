@@ -8,7 +8,8 @@ zeros for Hough voting and hard labels, as the reference registers them); the fi
 deconvs and the vertex loss have hand-written gfx950 backward kernels; convolutions / fc layers go
 through the framework's autograd. A trainable `vgg16_convs(is_train=True)` evaluates the heads in
 the reference's literal op order (the fused inference epilogues have no backward) unless it is built with
-`lowres_train_heads=True`: then the label head is `ops.label_head_loss`, which has one.
+`lowres_train_heads=True`: then the label head is `ops.label_head_loss`, which has one; with `fused_vertex_loss=True` on
+top and a `vertex_objects` feed the vertex head is `ops.vertex_head_loss` likewise.
 """
 import torch
 
@@ -89,7 +90,9 @@ def build_losses(net, cfg=TrainConfig):
     out["loss_regu"] = regularization_loss(net, cfg.WEIGHT_REG)
     loss = out["loss_cls"] + out["loss_regu"]
     if net.vertex_reg:
-        if "vertex_objects" in net.layers and "vertex_targets" not in net.layers:
+        if "loss_vertex_sl1" in net.layers:   # vgg16_convs(fused_vertex_loss=True): the loss left the vertex head's own kernel
+            out["loss_vertex"] = cfg.VERTEX_W * net.get_output("loss_vertex_sl1")
+        elif "vertex_objects" in net.layers and "vertex_targets" not in net.layers:
             # the feed of datasets.training_blobs: no [B,H,W,3C] targets, the loss reads label map + object table
             instance = net.get_output("vertex_instance") if "vertex_instance" in net.layers else None
             out["loss_vertex"] = cfg.VERTEX_W * smooth_l1_loss_vertex_gt(
