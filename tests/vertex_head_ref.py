@@ -27,6 +27,11 @@ import vertex_ref
 F = np.float32
 SL1_BLOCKS = 1024
 CASES = {"A": (2, 6, 11, 16, 8, 4, 3), "B": (1, 5, 7, 4, 2, 22, 5), "C": (3, 12, 16, 16, 8, 22, 5), "D": (1, 2, 3, 16, 8, 64, 5)}
+# The tile ladder of vertex_head_loss.hip (tests/bilinear_geometry.py, tests/GEOMETRY.md): one case per rung and the two
+# geometries no rung fits, 2 x 5 x 9 cells each so that the tiles of more than one cell are clipped in both directions.
+# Kept out of CASES: case_ids() and the tests parametrised over it stay as they were.
+GEOMETRY_CASES = {"G%d_%d" % ks: (2, 5, 9) + ks + (4, 3)
+                  for ks in ((16, 8), (20, 10), (14, 14), (32, 16), (28, 28), (40, 40), (64, 32), (56, 56))}
 KINDS = ("mixed", "empty", "full", "branches_sigma1", "branches_sigma3")
 MUTATIONS = ("bias_dropped", "row_priority_reversed", "taps_swapped")
 INSTANCE_ID = 7
@@ -46,8 +51,12 @@ def case(name, kind="mixed"):
               rows 3 and 4 are two unmasked rows of c4 (w 1, w 10): the higher wins everywhere.
     empty     labels from -1, 0, C only;  full: every pixel c1, one live row.
     branches  `mixed` with sigma 1 / 3 and z scaled so that both smooth-L1 branches occur (reference() asserts it)."""
-    B, H, W, k, s, C, M = CASES[name]
-    rng = np.random.default_rng([sorted(CASES).index(name), KINDS.index(kind), 20])
+    if name in CASES:
+        B, H, W, k, s, C, M = CASES[name]
+        rng = np.random.default_rng([sorted(CASES).index(name), KINDS.index(kind), 20])
+    else:
+        B, H, W, k, s, C, M = GEOMETRY_CASES[name]
+        rng = np.random.default_rng([100 + sorted(GEOMETRY_CASES).index(name), KINDS.index(kind), 20])
     Ho, Wo = H * s, W * s
     sigma = 3.0 if kind == "branches_sigma3" else 1.0
     scale = {"branches_sigma1": 1.5, "branches_sigma3": 0.4}.get(kind, 1.0)
