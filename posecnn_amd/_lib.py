@@ -1,6 +1,6 @@
 """ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h, include/posecnn_hip_train.h,
-include/posecnn_hip_frontend.h, include/posecnn_hip_synth.h, include/posecnn_hip_augment.h, include/posecnn_hip_loss.h and
-include/posecnn_hip_vertex_loss.h).
+include/posecnn_hip_frontend.h, include/posecnn_hip_synth.h, include/posecnn_hip_augment.h, include/posecnn_hip_loss.h,
+include/posecnn_hip_vertex_loss.h and include/posecnn_hip_trunk_train.h).
 
 This is the Python-side analogue of the reference's ``tf.load_op_library('<op>.so')`` stubs
 (lib/hough_voting_gpu_layer/hough_voting_gpu_op.py:4-7 and siblings). The library is built
@@ -163,6 +163,15 @@ VERTEX_LOSS_SIGNATURES = {
                                           _P, _P, _P, c_size_t, _P]),
 }
 
+# the training trunk-epilogue entries of include/posecnn_hip_trunk_train.h (same library, same ABI version)
+TRUNK_TRAIN_SIGNATURES = {
+    "pcnn_bias_relu_pool2_train_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "pcnn_bias_relu_train_workspace_bytes": (c_int, [c_int64, c_int, POINTER(c_size_t)]),
+    "pcnn_bias_relu_pool2_train_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "pcnn_bias_relu_pool2_train_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "pcnn_bias_relu_train_bwd": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+}
+
 
 def profile_enable(on=True):
     """Bracket every library kernel launch with HIP events on its launch stream."""
@@ -210,7 +219,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) +\
                 list(SYNTH_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) +\
-                list(VERTEX_LOSS_SIGNATURES.items()):
+                list(VERTEX_LOSS_SIGNATURES.items()) + list(TRUNK_TRAIN_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args

@@ -145,6 +145,7 @@ class _RawConv(object):
         self.lazy12 = lazy12
         self.dual = False
         self.pooled = None   # the 2x2 max-pool of `out`, when the producing kernel wrote both
+        self.train = None    # `y` as the framework convolution returned it ([B,C,H,W], channels_last), under fused_train_epilogue
 
     @property
     def shape(self):
@@ -167,6 +168,15 @@ class Network(object):
     Variables live in `self.vars` under '<layer>/weights' and '<layer>/biases' (the names
     tf.variable_scope + make_var give them, network.py:169-185) and are created on first use.
     """
+
+    # A training-graph switch, not an inference route: under autograd and on the GPU, bias + ReLU (+ the 2x2 max_pool) behind
+    # every framework convolution run as ops.bias_relu_train_ / ops.bias_relu_pool2_train (`_conv_train_epilogue`). Off for
+    # every network until `use_fused_train_epilogue` turns it on for that instance.
+    fused_train_epilogue = False
+
+    def use_fused_train_epilogue(self, on=True):
+        self.fused_train_epilogue = bool(on)
+        return self
 
     def __init__(self, device="cuda", seed=3, init="he", trainable=True):
         self.inputs = []
@@ -196,7 +206,7 @@ class Network(object):
         self.fused_conv12 = True      # conv1_1 -> conv1_2 -> pool1 as one LDS-resident kernel (round 4): the grouped RGB-D trunk, and
                                       # (lazily, when the max_pool arrives) every single tower
         self.defer_act = frozenset()  # conv layers whose bias + ReLU is left to the following max_pool
-        self.dual_pool = frozenset()  # ... and those whose un-pooled output other layers read too (Winograd only)
+        self.dual_pool = frozenset()  # ... and those whose un-pooled output other layers read too (Winograd, and the training epilogue)
         self.rows_count = None        # device int32[1]: true row count of capacity-sized ROI rows fed to `fc` (or None)
         self.fc_skinny = True         # <= 32 capacity rows: fc6-8 on the weight-streaming kernel (csrc/fc_skinny.hip)
         self.small_heads = True       # 1/8-resolution head algebra (deconv + add + 1x1) in one launch (csrc/heads_small.hip)
@@ -495,12 +505,16 @@ class Network(object):
         if self.conv_timing is not None and input.is_cuda:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            y = _nhwc(F.conv2d(_nchw(input), w, None, stride=(s_h, s_w), padding=pad, groups=group))
+            y = F.conv2d(_nchw(input), w, None, stride=(s_h, s_w), padding=pad, groups=group)
             e1.record()
             flops = 2.0 * y.numel() * (c_i // group) * k_h * k_w
             self.conv_timing.append((name, flops, flops, e0, e1))
         else:
-            y = _nhwc(F.conv2d(_nchw(input), w, None, stride=(s_h, s_w), padding=pad, groups=group))
+            y = F.conv2d(_nchw(input), w, None, stride=(s_h, s_w), padding=pad, groups=group)
+        if (b is not None and self.fused_train_epilogue and y.is_cuda and torch.is_grad_enabled()
+                and (y.requires_grad or b.requires_grad)):
+            return self._conv_train_epilogue(name, y, b, relu)
+        y = _nhwc(y)
         if b is not None and name in self.defer_act and not (torch.is_grad_enabled() and y.requires_grad):
             return _RawConv(y, b, relu)
         if b is None and not relu:
@@ -508,6 +522,24 @@ class Network(object):
         if b is None:
             return F.relu_(y)
         return self._bias_act(y, b, relu)  # bias_add + relu (network.py:181-187) in one pass, in place
+
+    def _conv_train_epilogue(self, name, y, b, relu):
+        """`fused_train_epilogue`: what follows the framework convolution `y` ([B,C,H,W], channels_last) under autograd, on the
+        library's own kernels (csrc/trunk_epilogue.hip). The epilogues write `y` itself — the convolution's result, not an
+        NHWC view of it, which autograd could only write in place by copying the whole tensor back and forth."""
+        if not y.is_contiguous(memory_format=torch.channels_last):
+            y = y.contiguous(memory_format=torch.channels_last)
+        even = y.shape[2] % 2 == 0 and y.shape[3] % 2 == 0
+        if name in self.defer_act and even:
+            out = _RawConv(_nhwc(y), b, relu)   # the following max_pool decides (ops.bias_relu_pool2_train)
+            out.train = y
+            return out
+        if name in self.dual_pool and even and relu:
+            out = _RawConv(None, b, relu)
+            act, pooled = ops.bias_relu_pool2_train(y, b, True, want_act=True)
+            out.out, out.pooled = _nhwc(act), _nhwc(pooled)
+            return out
+        return _nhwc(ops.bias_relu_train_(y, b, relu))
 
     @layer
     def max_pool(self, input, k_h, k_w, s_h, s_w, name, padding=DEFAULT_PADDING):
@@ -540,6 +572,8 @@ class Network(object):
                 if input.wino is not None:  # a Winograd output tile is exactly one pooling window
                     m, B_, H_, W_ = input.wino
                     return ops.winograd_output(m, input.bias, B_, H_, W_, input.relu, pool=True, tile=self.winograd_tile)
+                if input.train is not None:   # fused_train_epilogue: one byte per pooled element is all the backward keeps
+                    return _nhwc(ops.bias_relu_pool2_train(input.train, input.bias, input.relu))
                 return self._bias_relu_pool2(input.y, input.bias, input.relu)
             input = self._activate(input)
         H, W = input.shape[1], input.shape[2]
@@ -801,7 +835,8 @@ class vgg16_convs(Network):
     def __init__(self, input_format, num_classes, num_units, scales, threshold_label, vote_threshold,
                  vertex_reg_2d=False, vertex_reg_3d=False, pose_reg=False, adaptation=False, trainable=True,
                  is_train=True, device="cuda", seed=3, init="he", with_losses=None, fused_heads=True,
-                 want_prob=True, fused_pool=True, strict_numerics=False, lowres_train_heads=False, fused_vertex_loss=False):
+                 want_prob=True, fused_pool=True, strict_numerics=False, lowres_train_heads=False, fused_vertex_loss=False,
+                 fused_train_epilogue=False):
         Network.__init__(self, device=device, seed=seed, init=init, trainable=trainable)
         # strict_numerics: every 3x3 layer as a direct f32 convolution (library kernels) instead of Winograd
         # F(4x4,3x3). Both are exact in real arithmetic and f32 throughout; they differ in summation order
@@ -837,6 +872,13 @@ class vgg16_convs(Network):
         # kernel each way, csrc/vertex_head_loss.hip) as `loss_vertex_sl1`, the Hough layer reads the 1/8-resolution field as
         # in inference, and `vertex_pred` is only built if somebody fetches it. Any other feed builds today's graph.
         self.fused_vertex_loss = bool(fused_vertex_loss and self.lowres_train_heads)
+        # fused_train_epilogue (opt-in, trainable training graphs only, independent of the two switches above): under autograd
+        # and on the GPU, what follows every biased convolution runs on csrc/trunk_epilogue.hip instead of the framework's
+        # bias_add, ReLU and max_pool2d: the conv -> pool pairs of `defer_act` as ops.bias_relu_pool2_train (the backward keeps
+        # one byte per pooled element; no activated full-resolution tensor, no int64 indices), conv4_3 (`dual_pool`) as its
+        # dual form, every other layer — the 1x1 score convolutions included — as the in-place ops.bias_relu_train_. The
+        # bias gradients come out of the same passes. Same variables, same layer names.
+        self.use_fused_train_epilogue(fused_train_epilogue and is_train and trainable)
         self.want_prob = want_prob  # prob_normalized is a fetched output in lib/fcn/test.py:193-195
         self.input_format = input_format
         self.num_classes = num_classes

@@ -25,6 +25,7 @@ __all__ = [
     "upscore_softmax_argmax", "Workspace", "vertex_targets", "smooth_l1_loss_vertex_gt",
     "depth_normals", "bilateral_filter_u8", "normal_image", "bilateral_tables", "augment_frames",
     "label_head_loss", "label_head_loss_grad", "vertex_head_loss", "vertex_head_loss_grad",
+    "bias_relu_train_", "bias_relu_train_grad", "bias_relu_pool2_train", "bias_relu_pool2_train_grad",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1185,6 +1186,176 @@ def vertex_head_loss(z, bias, gt_label_2d, objects, kernel, stride, instance=Non
     sums f32 [2] = (sum(in_loss), sum(w))). Differentiable w.r.t. z and bias; z and bias must be finite."""
     z, bias, label, obj, instance, _ = _vertex_head_loss_args(z, bias, gt_label_2d, objects, instance, kernel, stride)
     return _VertexHeadLossFn.apply(z, bias, label, obj, instance, int(kernel), int(stride), float(sigma))
+
+
+# ---- the trunk's training epilogues (include/posecnn_hip_trunk_train.h, csrc/trunk_epilogue.hip) ---------------------------
+def _channels_first(t):
+    """Is `t` a 4-D [B,C,H,W] tensor whose memory is NHWC-dense (channels_last) — what the framework's convolution returns
+    for the NHWC activations of this package? The epilogues take it as it is: an NHWC *view* of it could not be written in
+    place without autograd copying the whole tensor back and forth. A tensor that is contiguous as it stands is NHWC."""
+    return t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
+
+
+def _trunk_dbias_ws(fn_name, shape, device, want):
+    if not want:
+        return None, None
+    nbytes = c_size_t(0)
+    check(fn_name, getattr(lib(), fn_name)(*(tuple(shape) + (ctypes.byref(nbytes),))))
+    C = shape[-1]
+    return torch.empty(C, dtype=torch.float32, device=device), _ws(device, "trunk_epilogue").get(nbytes.value, device)
+
+
+def bias_relu_train_grad(da, a, relu=True, want_dbias=True):
+    """The backward kernel of `bias_relu_train_` on its own: -> (dy, dbias f32 [C] | None) from the gradient `da` and the
+    layer's output `a`, both [..., C] contiguous (`a` may be None when `relu` is off): dy = relu ? (a > 0 ? da : 0) : da,
+    dbias the sum of dy over pixels in the order of the header."""
+    da = _dev(da, "da", torch.float32)
+    a = _dev(a, "a", torch.float32) if a is not None else None
+    if relu and (a is None or a.shape != da.shape):
+        raise ValueError("a must have da's shape %s (got %s)" % (tuple(da.shape), None if a is None else tuple(a.shape)))
+    if da.dim() < 2:
+        raise ValueError("da must be [..., C]")
+    C = da.shape[-1]
+    rows = da.numel() // C
+    dy = torch.empty_like(da)
+    dbias, ws = _trunk_dbias_ws("pcnn_bias_relu_train_workspace_bytes", (rows, C), da.device, want_dbias)
+    check("pcnn_bias_relu_train_bwd",
+          lib().pcnn_bias_relu_train_bwd(_ptr(da), _ptr(a if relu else None), rows, C, 1 if relu else 0, _ptr(dy), _ptr(dbias),
+                                         _ptr(ws), ws.numel() if ws is not None else 0, _stream(da)))
+    return dy, dbias
+
+
+class _BiasReluTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, bias, relu):
+        cf = _channels_first(y)
+        bias_act_(y.permute(0, 2, 3, 1) if cf else y, bias, relu)
+        ctx.mark_dirty(y)
+        ctx.cfg = (relu, cf)
+        ctx.save_for_backward(*((y,) if relu else ()))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        relu, cf = ctx.cfg
+        a = ctx.saved_tensors[0] if relu else None
+        if cf:
+            grad, a = grad.permute(0, 2, 3, 1), (a.permute(0, 2, 3, 1) if relu else None)
+        dy, dbias = bias_relu_train_grad(grad, a, relu, want_dbias=ctx.needs_input_grad[1])
+        return (dy.permute(0, 3, 1, 2) if cf else dy), dbias, None
+
+
+def bias_relu_train_(y, bias, relu=True):
+    """`bias_act_` under autograd: in place y[..., c] = [ReLU](y[..., c] + bias[c]), differentiable w.r.t. y and bias, one
+    kernel each way; the output itself is what the backward keeps. `y` is NHWC-contiguous [..., C], or the channels_last
+    [B,C,H,W] result of a framework convolution (returned in the same form); it must not be a leaf that requires grad."""
+    y = _dev_dense(y, "y")
+    bias = _dev(bias, "bias", torch.float32)
+    C = y.shape[1] if _channels_first(y) else y.shape[-1]
+    if bias.dim() != 1 or bias.numel() != C:
+        raise ValueError("bias must have one entry per channel (%d, got %s)" % (C, tuple(bias.shape)))
+    return _BiasReluTrainFn.apply(y, bias, bool(relu))
+
+
+def _dev_dense(t, name):
+    """`_dev` without its copy: the in-place epilogues write the tensor they are given."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        _dev(t, name, torch.float32)
+    if not (t.is_contiguous() or _channels_first(t)):
+        raise ValueError("%s must be contiguous as NHWC, or channels_last as [B,C,H,W] (got strides %s)" % (name, t.stride()))
+    return t
+
+
+def _bias_relu_pool2_train_raw(y, bias, relu=True, want_act=False):
+    """-> (act | None, pooled f32 [B,H/2,W/2,C], sel u8 [B,H/2,W/2,C]): one call of pcnn_bias_relu_pool2_train_fwd on the
+    NHWC-contiguous y; with `want_act`, act IS y, overwritten."""
+    y = _dev(y, "y", torch.float32)
+    bias = _dev(bias, "bias", torch.float32)
+    if y.dim() != 4 or bias.dim() != 1 or bias.shape[0] != y.shape[3]:
+        raise ValueError("y must be [B,H,W,C] and bias [C] (got %s, %s)" % (tuple(y.shape), tuple(bias.shape)))
+    B, H, W, C = y.shape
+    pooled = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=y.device)
+    sel = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8, device=y.device)
+    act = y if want_act else None
+    check("pcnn_bias_relu_pool2_train_fwd",
+          lib().pcnn_bias_relu_pool2_train_fwd(_ptr(y), _ptr(bias), B, H, W, C, 1 if relu else 0, _ptr(act), _ptr(pooled),
+                                               _ptr(sel), _stream(y)))
+    return act, pooled, sel
+
+
+def bias_relu_pool2_train_grad(dpooled, sel, dact=None, act=None, want_dbias=True):
+    """The backward kernel of `bias_relu_pool2_train` on its own: -> (dy f32 [B,H,W,C], dbias f32 [C] | None) from dpooled
+    f32 and sel u8 [B,H/2,W/2,C] and, for the dual form, the gradient and the value of the activated tensor [B,H,W,C]:
+    dy_k = (act_k > 0 ? dact_k : 0) + (sel == k ? dpooled : 0)."""
+    dpooled = _dev(dpooled, "dpooled", torch.float32)
+    sel = _dev(sel, "sel", torch.uint8)
+    if dpooled.dim() != 4 or sel.shape != dpooled.shape:
+        raise ValueError("dpooled and sel must both be [B,H/2,W/2,C] (got %s, %s)" % (tuple(dpooled.shape), tuple(sel.shape)))
+    B, Ho, Wo, C = dpooled.shape
+    H, W = 2 * Ho, 2 * Wo
+    if (dact is None) != (act is None):
+        raise ValueError("dact and act are both None or both given")
+    if dact is not None:
+        dact, act = _dev(dact, "dact", torch.float32), _dev(act, "act", torch.float32)
+        if tuple(dact.shape) != (B, H, W, C) or act.shape != dact.shape:
+            raise ValueError("dact and act must be %s (got %s, %s)" % ((B, H, W, C), tuple(dact.shape), tuple(act.shape)))
+    dy = torch.empty((B, H, W, C), dtype=torch.float32, device=dpooled.device)
+    dbias, ws = _trunk_dbias_ws("pcnn_bias_relu_pool2_train_workspace_bytes", (B, H, W, C), dpooled.device, want_dbias)
+    check("pcnn_bias_relu_pool2_train_bwd",
+          lib().pcnn_bias_relu_pool2_train_bwd(_ptr(dpooled), _ptr(sel), _ptr(dact), _ptr(act), B, H, W, C, _ptr(dy), _ptr(dbias),
+                                               _ptr(ws), ws.numel() if ws is not None else 0, _stream(dpooled)))
+    return dy, dbias
+
+
+class _BiasReluPool2TrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, bias, relu, want_act):
+        cf = _channels_first(y)
+        act, pooled, sel = _bias_relu_pool2_train_raw(y.permute(0, 2, 3, 1) if cf else y, bias, relu, want_act)
+        ctx.cf = cf
+        ctx.set_materialize_grads(False)
+        if cf:
+            pooled = pooled.permute(0, 3, 1, 2)
+        if not want_act:
+            ctx.save_for_backward(sel)
+            return pooled
+        ctx.mark_dirty(y)
+        ctx.save_for_backward(sel, y)
+        return y, pooled
+
+    @staticmethod
+    def backward(ctx, *grads):
+        sel = ctx.saved_tensors[0]
+        dact, dpooled = grads if len(grads) == 2 else (None, grads[0])
+        nhwc = (lambda t: t.permute(0, 2, 3, 1)) if ctx.cf else (lambda t: t)
+        act = nhwc(ctx.saved_tensors[1]) if dact is not None else None
+        dpooled = nhwc(dpooled) if dpooled is not None else torch.zeros(sel.shape, dtype=torch.float32, device=sel.device)
+        dy, dbias = bias_relu_pool2_train_grad(dpooled, sel, nhwc(dact) if dact is not None else None, act,
+                                               want_dbias=ctx.needs_input_grad[1])
+        return (dy.permute(0, 3, 1, 2) if ctx.cf else dy), dbias, None, None
+
+
+def bias_relu_pool2_train(y, bias, relu=True, want_act=False):
+    """The conv -> pool pairs of the trunk under autograd: pooled = max_pool_2x2([ReLU](y + bias)) from the raw convolution
+    output y [B,H,W,C] (H, W even), one kernel each way. What the backward keeps is one byte per pooled element (which
+    of the window's four values it was, or that the ReLU closed the window): neither the activated full-resolution tensor nor
+    an index tensor exists. With `want_act` (conv4_3, whose un-pooled output other layers read) returns (act, pooled), act
+    being y overwritten in place and kept for the backward; only the ReLU form has that backward. `y` is NHWC-contiguous, or
+    the channels_last [B,C,H,W] result of a framework convolution (the outputs then come in the same form).
+    Differentiable w.r.t. y and bias."""
+    if want_act and not relu:
+        raise ValueError("bias_relu_pool2_train(want_act=True) is the ReLU layer's form: its backward gates on act > 0")
+    if isinstance(y, torch.Tensor) and (want_act or _channels_first(y)):
+        y = _dev_dense(y, "y")
+    else:
+        y = _dev(y, "y", torch.float32)
+    bias = _dev(bias, "bias", torch.float32)
+    if y.dim() != 4:
+        raise ValueError("y must be [B,H,W,C] (got %s)" % (tuple(y.shape),))
+    C = y.shape[1] if _channels_first(y) else y.shape[-1]
+    if bias.dim() != 1 or bias.numel() != C:
+        raise ValueError("bias must have one entry per channel (%d, got %s)" % (C, tuple(bias.shape)))
+    return _BiasReluPool2TrainFn.apply(y, bias, bool(relu), bool(want_act))
 
 
 # ------------------------------------------------------------------------------------------------

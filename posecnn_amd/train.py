@@ -9,7 +9,10 @@ deconvs and the vertex loss have hand-written gfx950 backward kernels; convoluti
 through the framework's autograd. A trainable `vgg16_convs(is_train=True)` evaluates the heads in
 the reference's literal op order (the fused inference epilogues have no backward) unless it is built with
 `lowres_train_heads=True`: then the label head is `ops.label_head_loss`, which has one; with `fused_vertex_loss=True` on
-top and a `vertex_objects` feed the vertex head is `ops.vertex_head_loss` likewise.
+top and a `vertex_objects` feed the vertex head is `ops.vertex_head_loss` likewise. Independently of both,
+`fused_train_epilogue=True` takes the bias_add / ReLU / 2x2 max-pool that follow every convolution off the framework's
+elementwise kernels: `ops.bias_relu_train_` and `ops.bias_relu_pool2_train`, one kernel each way with the bias gradient in
+the same pass (csrc/trunk_epilogue.hip). The variables are the same under every combination of the three switches.
 """
 import torch
 
