@@ -1,6 +1,7 @@
 // bilinear.h — tap tables of PoseCNN's fixed bilinear "deconv" layers (lib/networks/network.py:141-157
-// make_deconv_filter), shared by the deconv / label-head kernels (upscore.hip) and by the Hough
-// voting kernel that interpolates the 1/8-resolution vertex field on the fly (hough_voting.hip).
+// make_deconv_filter), shared by the deconv kernels (upscore.hip), the label heads (label_head_device.h),
+// the training vertex head (vertex_head_loss.hip) and by the Hough voting kernel that interpolates the
+// 1/8-resolution vertex field on the fly (hough_voting.hip).
 // Every user accumulates in the same canonical order — input rows ascending, input columns
 // ascending, acc = acc + (wy*wx)*in, then + bias — so all of them produce identical bits.
 #pragma once
@@ -22,8 +23,10 @@ struct Taps {
   float w[4];      // tap weights for i0, i0+1, ...
 };
 
-// output index o of a SAME conv2d_transpose (pad = (k - s) / 2): o = s*i + t - pad, 0 <= t < k
-__device__ __forceinline__ Taps make_taps(int o, int k, int s, int pad, int n_in)
+// output index o of a SAME conv2d_transpose (pad = (k - s) / 2): o = s*i + t - pad, 0 <= t < k.
+// weight(t) is the tap value bilinear_tap(t, k), wherever the caller has it from.
+template <class Weight>
+__device__ __forceinline__ Taps make_taps_from(int o, int k, int s, int pad, int n_in, Weight weight)
 {
   Taps T;
   const int a = o + pad;
@@ -36,27 +39,20 @@ __device__ __forceinline__ Taps make_taps(int o, int k, int s, int pad, int n_in
   T.n = hi - lo + 1;
   if (T.n < 0) T.n = 0;
 #pragma unroll
-  for (int j = 0; j < 4; j++) T.w[j] = j < T.n ? bilinear_tap(a - s * (lo + j), k) : 0.f;
+  for (int j = 0; j < 4; j++) T.w[j] = j < T.n ? weight(a - s * (lo + j)) : 0.f;
   return T;
 }
 
-// make_taps with the k tap values bilinear_tap(t, k), t = 0 .. k-1, read from a table (LDS) instead of being evaluated in
-// double precision per call: same integers, same f32 weights.
+// the tap values evaluated in double precision per call
+__device__ __forceinline__ Taps make_taps(int o, int k, int s, int pad, int n_in)
+{
+  return make_taps_from(o, k, s, pad, n_in, [k](int t) { return bilinear_tap(t, k); });
+}
+
+// the k tap values bilinear_tap(t, k), t = 0 .. k-1, read from a table (LDS): same integers, same f32 weights
 __device__ __forceinline__ Taps make_taps_tab(int o, int k, int s, int pad, int n_in, const float* tab)
 {
-  Taps T;
-  const int a = o + pad;
-  int lo = (a - k + 1 + s - 1) / s;
-  if (a - k + 1 < 0) lo = -((k - 1 - a) / s);
-  int hi = a / s;
-  if (lo < 0) lo = 0;
-  if (hi > n_in - 1) hi = n_in - 1;
-  T.i0 = lo;
-  T.n = hi - lo + 1;
-  if (T.n < 0) T.n = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) T.w[j] = j < T.n ? tab[a - s * (lo + j)] : 0.f;
-  return T;
+  return make_taps_from(o, k, s, pad, n_in, [tab](int t) { return tab[t]; });
 }
 
 // One output element of deconv(in)[+ bias] for channel c at output pixel (oy, ox); `inb` points at

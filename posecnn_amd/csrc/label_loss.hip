@@ -9,19 +9,19 @@
 //   pcnn_label_head_loss_fwd   label, optional per-pixel terms, loss = S / (count + 1e-10); no [B,Ho,Wo,C] tensor written
 //   pcnn_label_head_loss_bwd   dscore [B,Ho,Wo,C] (the one such tensor of the pair) and dbias; dz is pcnn_deconv_bilinear_bwd
 //
-// Arithmetic per pixel: the expression trees of upscore_softmax_argmax_kernel, in its order — same bits for label and
+// Segment, per-pixel arithmetic and tile plan are the label head's own (label_head_device.h) — same bits for label and
 // prob (the CPU checker builds the expected terms from the oracle's probabilities). Reductions: f64, fixed order, no
-// atomics (see the header).
+// atomics (see the header; reduce_device.h).
 #include "../../include/posecnn_hip_loss.h"
-#include "bilinear.h"
+#include "label_head_device.h"
+#include "reduce_device.h"
 
 namespace {
 
 using namespace pcnn;
 
-constexpr int LL_SEG = 128;   // pixels (= threads) per workgroup, as UP_SEG
-constexpr int LL_RUNS = 4;    // dbias: runs of LL_SEG / LL_RUNS consecutive pixels per workgroup
-constexpr int LL_FIN = 256;   // threads of the final kernels
+constexpr int LL_RUNS = 4;    // dbias: runs of LH_SEG / LL_RUNS consecutive pixels per workgroup
+constexpr int LL_FIN = 256;   // threads of the forward's final kernel
 
 // log of a softmax denominator, x in [1, 64]: a fixed sequence of IEEE f32 operations like exp_softmax_f32, restated by
 // tests/label_loss_ref.py one numpy operation per line. x = 2^n t with t in [sqrt(1/2), sqrt(2)); log t = 2 atanh(q),
@@ -50,120 +50,6 @@ __device__ __forceinline__ float log_sum_f32(float x)
   return nf * 0.693145752f + (l + nf * 1.42860677e-06f);
 }
 
-// What both directions need of one pixel. e[] leaves as the probabilities; `pos` has bit c set where score[c] > 0.
-struct Pixel {
-  float sum, dg, pg;   // softmax denominator; score[g] - m and prob[g] of the ground-truth class (0 when g < 0)
-  int best;
-  unsigned long long pos;
-};
-
-// CT > 0: the class count at compile time (everything unrolls, scores stay in registers); CT == 0: C at run time, every
-// channel operation guarded by c < C. The tap loops are unrolled with guards either way: runtime bounds would index the
-// tap arrays dynamically and put them in scratch memory (upscore.hip).
-template <int CT, int CMAX>
-__device__ __forceinline__ Pixel eval_pixel(const float* s_z, const float* __restrict__ bias, const Taps& ty, const Taps& tx,
-                                            int ncx, int cx0, int Crt, int relu, int g, float (&e)[CMAX])
-{
-  const int C = CT > 0 ? CT : Crt;
-  Pixel P;
-#pragma unroll
-  for (int c = 0; c < CMAX; c++) e[c] = 0.f;
-#pragma unroll
-  for (int jy = 0; jy < 4; jy++)
-    if (jy < ty.n) {
-#pragma unroll
-      for (int jx = 0; jx < 4; jx++)
-        if (jx < tx.n) {
-          const float w = ty.w[jy] * tx.w[jx];
-          const float* zc = s_z + (jy * ncx + (tx.i0 + jx - cx0)) * C;
-#pragma unroll
-          for (int c = 0; c < CMAX; c++)
-            if (c < C) e[c] = e[c] + w * zc[c];
-        }
-    }
-  P.pos = 0ull;
-#pragma unroll
-  for (int c = 0; c < CMAX; c++)
-    if (c < C) {
-      float v = e[c] + bias[c];
-      if (relu) v = v > 0.f ? v : 0.f;
-      if (v > 0.f) P.pos |= 1ull << c;
-      e[c] = v;
-    }
-  float m = e[0];
-#pragma unroll
-  for (int c = 0; c < CMAX; c++)
-    if (c < C) m = fmaxf(m, e[c]);
-  float sum = 0.f;
-  P.dg = 0.f;
-#pragma unroll
-  for (int c = 0; c < CMAX; c++)
-    if (c < C) {
-      const float d = e[c] - m;
-      if (c == g) P.dg = d;
-      e[c] = exp_softmax_f32(d);
-      sum += e[c];
-    }
-  float bestp = div_rn(e[0], sum);
-  P.best = 0;
-  P.pg = 0.f;
-#pragma unroll
-  for (int c = 0; c < CMAX; c++)
-    if (c < C) {
-      const float p = div_rn(e[c], sum);
-      e[c] = p;
-      if (c == g) P.pg = p;
-      if (p > bestp) { bestp = p; P.best = c; }
-    }
-  P.sum = sum;
-  return P;
-}
-
-// The segment's geometry and its low-resolution cells in LDS: what upscore_softmax_argmax_kernel does before its first
-// barrier. Must be called by every thread of the workgroup.
-struct Segment {
-  int b, oy, ox0, npx, cx0, ncx;
-  Taps ty;
-};
-
-__device__ __forceinline__ Segment load_segment(const float* __restrict__ z, float* s_z, float* s_tab, int H, int W, int C,
-                                                int k, int s, int nseg)
-{
-  Segment S;
-  const int pad = (k - s) / 2;
-  const int Ho = H * s, Wo = W * s;
-  const int tid = threadIdx.x;
-  S.b = blockIdx.x / (nseg * Ho);
-  S.oy = (blockIdx.x / nseg) % Ho;
-  S.ox0 = (blockIdx.x % nseg) * LL_SEG;
-  S.npx = min(LL_SEG, Wo - S.ox0);
-  if (tid < k) s_tab[tid] = bilinear_tap(tid, k);
-  __syncthreads();
-  S.ty = make_taps_tab(S.oy, k, s, pad, H, s_tab);
-  const Taps tfirst = make_taps_tab(S.ox0, k, s, pad, W, s_tab);
-  const Taps tlast = make_taps_tab(S.ox0 + S.npx - 1, k, s, pad, W, s_tab);
-  S.cx0 = tfirst.i0;
-  S.ncx = tlast.i0 + (tlast.n > 0 ? tlast.n : 1) - S.cx0;
-  // a row's ncx cells x C channels are one contiguous run of z; four loads per thread issued before the first LDS write
-  const int rowlen = S.ncx * C;
-  const int tot = S.ty.n * rowlen;
-  const float* src0 = z + (((long long)S.b * H + S.ty.i0) * W + S.cx0) * C;
-  for (int e0 = tid; e0 < tot; e0 += 4 * LL_SEG) {
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int e = min(e0 + j * LL_SEG, tot - 1);
-      const int ry = e / rowlen, i = e - ry * rowlen;
-      v[j] = src0[(long long)ry * W * C + i];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-      if (e0 + j * LL_SEG < tot) s_z[e0 + j * LL_SEG] = v[j];
-  }
-  __syncthreads();
-  return S;
-}
-
 __device__ __forceinline__ bool hot_class(int g, float pg, float threshold)
 {
   // hard_label_op_gpu.cu.cc:17-29; g < 0 here also stands for a label outside [0, C), ignored as in up_hard_label_rows
@@ -171,15 +57,15 @@ __device__ __forceinline__ bool hot_class(int g, float pg, float threshold)
 }
 
 template <int CT, int CMAX>
-__global__ __launch_bounds__(LL_SEG) void label_loss_fwd_kernel(
+__global__ __launch_bounds__(LH_SEG) void label_loss_fwd_kernel(
     const float* __restrict__ z, const float* __restrict__ bias, const int* __restrict__ gt, int* __restrict__ label,
     float* __restrict__ terms, double* __restrict__ part_s, long long* __restrict__ part_n, int H, int W, int Crt, int k,
     int s, int relu, int nseg, float threshold)
 {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float s_tab[64];
-  __shared__ double s_sum[LL_SEG];
-  __shared__ int s_cnt[LL_SEG];
+  __shared__ double s_sum[LH_SEG];
+  __shared__ int s_cnt[LH_SEG];
   const int C = CT > 0 ? CT : Crt;
   const int tid = threadIdx.x;
   const Segment S = load_segment(z, smem, s_tab, H, W, C, k, s, nseg);
@@ -192,7 +78,8 @@ __global__ __launch_bounds__(LL_SEG) void label_loss_fwd_kernel(
     if (g < 0 || g >= C) g = -1;
     const Taps tx = make_taps_tab(S.ox0 + tid, k, s, (k - s) / 2, W, s_tab);
     float e[CMAX];
-    const Pixel P = eval_pixel<CT, CMAX>(smem, bias, S.ty, tx, S.ncx, S.cx0, C, relu, g, e);
+    interp_scores<CT, CMAX>(smem, bias, S.ty, tx, S.ncx, S.cx0, C, relu, e);
+    const Softmax P = softmax_argmax<CT, CMAX>(e, C, g);
     label[pix] = P.best;
     if (hot_class(g, P.pg, threshold)) {
       hot = 1;
@@ -202,14 +89,7 @@ __global__ __launch_bounds__(LL_SEG) void label_loss_fwd_kernel(
   }
   s_sum[tid] = (double)term;
   s_cnt[tid] = hot;
-  __syncthreads();
-  for (int st = LL_SEG / 2; st >= 1; st >>= 1) {
-    if (tid < st) {
-      s_sum[tid] = s_sum[tid] + s_sum[tid + st];
-      s_cnt[tid] = s_cnt[tid] + s_cnt[tid + st];
-    }
-    __syncthreads();
-  }
+  block_tree_sum<LH_SEG>(s_sum, s_cnt, tid);
   if (tid == 0) {
     part_s[blockIdx.x] = s_sum[0];
     part_n[blockIdx.x] = (long long)s_cnt[0];
@@ -231,14 +111,7 @@ __global__ __launch_bounds__(LL_FIN) void label_loss_fwd_final_kernel(const doub
   }
   s_sum[t] = a;
   s_cnt[t] = n;
-  __syncthreads();
-  for (int st = LL_FIN / 2; st >= 1; st >>= 1) {
-    if (t < st) {
-      s_sum[t] = s_sum[t] + s_sum[t + st];
-      s_cnt[t] = s_cnt[t] + s_cnt[t + st];
-    }
-    __syncthreads();
-  }
+  block_tree_sum<LL_FIN>(s_sum, s_cnt, t);
   if (t == 0) {
     sums[0] = s_sum[0];
     sums[1] = (double)s_cnt[0];
@@ -247,7 +120,7 @@ __global__ __launch_bounds__(LL_FIN) void label_loss_fwd_final_kernel(const doub
 }
 
 template <int CT, int CMAX>
-__global__ __launch_bounds__(LL_SEG) void label_loss_bwd_kernel(
+__global__ __launch_bounds__(LH_SEG) void label_loss_bwd_kernel(
     const float* __restrict__ z, const float* __restrict__ bias, const int* __restrict__ gt,
     const double* __restrict__ sums, const float* __restrict__ upstream, float* __restrict__ dscore,
     double* __restrict__ part_b, int H, int W, int Crt, int k, int s, int relu, int nseg, int s_out_off, float threshold)
@@ -258,7 +131,7 @@ __global__ __launch_bounds__(LL_SEG) void label_loss_bwd_kernel(
   const int C = CT > 0 ? CT : Crt;
   const int tid = threadIdx.x;
   const Segment S = load_segment(z, smem, s_tab, H, W, C, k, s, nseg);
-  float* s_out = smem + s_out_off;   // [LL_SEG][C]
+  float* s_out = smem + s_out_off;   // [LH_SEG][C]
   const int Wo = W * s;
   const long long pix0 = ((long long)S.b * H * s + S.oy) * Wo + S.ox0;
   if (tid < S.npx) {
@@ -267,13 +140,15 @@ __global__ __launch_bounds__(LL_SEG) void label_loss_bwd_kernel(
     if (g < 0 || g >= C) g = -1;
     const Taps tx = make_taps_tab(S.ox0 + tid, k, s, (k - s) / 2, W, s_tab);
     float e[CMAX];
-    const Pixel P = eval_pixel<CT, CMAX>(smem, bias, S.ty, tx, S.ncx, S.cx0, C, relu, g, e);
+    unsigned long long pos;   // bit c: score[c] > 0
+    interp_scores<CT, CMAX>(smem, bias, S.ty, tx, S.ncx, S.cx0, C, relu, e, &pos);
+    const Softmax P = softmax_argmax<CT, CMAX>(e, C, g);
     const bool hot = hot_class(g, P.pg, threshold);
 #pragma unroll
     for (int c = 0; c < CMAX; c++)
       if (c < C) {
         float d = coef * (e[c] - (c == g ? 1.0f : 0.0f));
-        if (!hot || (relu && !((P.pos >> c) & 1ull))) d = 0.f;   // the ReLU's gradient at score == 0 is zero
+        if (!hot || (relu && !((pos >> c) & 1ull))) d = 0.f;   // the ReLU's gradient at score == 0 is zero
         s_out[tid * C + c] = d;
       }
   }
@@ -282,16 +157,15 @@ __global__ __launch_bounds__(LL_SEG) void label_loss_bwd_kernel(
     // the segment's npx * C floats are one contiguous run of dscore; the deconv gradient reads them next: ordinary stores
     float* o = dscore + pix0 * C;
     const int nfl = S.npx * C;
-    typedef float v4f __attribute__((ext_vector_type(4)));
     if ((nfl & 3) == 0 && (s_out_off & 3) == 0 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-      for (int i = tid * 4; i < nfl; i += LL_SEG * 4) *reinterpret_cast<v4f*>(o + i) = *reinterpret_cast<const v4f*>(s_out + i);
+      for (int i = tid * 4; i < nfl; i += LH_SEG * 4) *reinterpret_cast<v4f*>(o + i) = *reinterpret_cast<const v4f*>(s_out + i);
     } else {
-      for (int i = tid; i < nfl; i += LL_SEG) o[i] = s_out[i];
+      for (int i = tid; i < nfl; i += LH_SEG) o[i] = s_out[i];
     }
   }
   // dbias partials: LL_RUNS runs of consecutive pixels per class, ascending inside a run, then the runs ascending
-  constexpr int RUN = LL_SEG / LL_RUNS;
-  for (int idx = tid; idx < C * LL_RUNS; idx += LL_SEG) {
+  constexpr int RUN = LH_SEG / LL_RUNS;
+  for (int idx = tid; idx < C * LL_RUNS; idx += LH_SEG) {
     const int c = idx % C, q = idx / C;
     const int p1 = min((q + 1) * RUN, S.npx);
     double a = 0.0;
@@ -307,28 +181,9 @@ __global__ __launch_bounds__(LL_SEG) void label_loss_bwd_kernel(
   }
 }
 
-// one workgroup per class
-__global__ __launch_bounds__(LL_FIN) void label_loss_bwd_final_kernel(const double* __restrict__ part_b, int nblk,
-                                                                      float* __restrict__ dbias)
-{
-  __shared__ double s_sum[LL_FIN];
-  const int t = threadIdx.x;
-  const double* p = part_b + (size_t)blockIdx.x * nblk;
-  double a = 0.0;
-  for (int i = t; i < nblk; i += LL_FIN) a = a + p[i];
-  s_sum[t] = a;
-  __syncthreads();
-  for (int st = LL_FIN / 2; st >= 1; st >>= 1) {
-    if (t < st) s_sum[t] = s_sum[t] + s_sum[t + st];
-    __syncthreads();
-  }
-  if (t == 0) dbias[blockIdx.x] = (float)s_sum[0];
-}
-
-struct Plan {
-  int nseg, s_out_off;
-  long long blocks;
-  size_t sh_fwd, sh_bwd, ws_bytes;
+// the label head's tile (the forward stages the cells only: sh_in; the backward parks dscore rows as well: sh_all)
+struct Plan : LabelHeadPlan {
+  size_t ws_bytes;
 };
 
 int make_plan(const char* who, int B, int H, int W, int C, int k, int s, Plan* p)
@@ -340,15 +195,9 @@ int make_plan(const char* who, int B, int H, int W, int C, int k, int s, Plan* p
                "%s: need stride >= 1, stride <= kernel <= min(4*stride, 64) and (kernel - stride) even (got kernel=%d stride=%d)",
                who, k, s);
   PCNN_REQUIRE((long long)B * H * s * W * s < (1ll << 31), PCNN_EINVAL, "%s: batch*height*width*stride^2 must be < 2^31", who);
-  const int Wo = W * s, Ho = H * s;
-  p->nseg = (Wo + LL_SEG - 1) / LL_SEG;
-  p->blocks = (long long)B * Ho * p->nseg;
-  const int rows = (k + s - 1) / s;                      // input rows per output row
-  const int ncx_max = (LL_SEG - 1) / s + rows + 1;       // input columns per segment
-  p->s_out_off = (rows * ncx_max * C + 3) / 4 * 4;
-  p->sh_fwd = sizeof(float) * (size_t)p->s_out_off;
-  p->sh_bwd = sizeof(float) * ((size_t)p->s_out_off + (size_t)LL_SEG * C);
-  PCNN_REQUIRE(p->sh_bwd + 4096 <= 160 * 1024, PCNN_EINVAL, "%s: tile does not fit LDS (kernel=%d stride=%d num_classes=%d)", who, k, s, C);
+  static_cast<LabelHeadPlan&>(*p) = label_head_plan(B, H, W, C, k, s);
+  // + 4096: the static arrays of the two kernels (tap table, reduction leaves, dbias runs) share the 160 KB
+  PCNN_REQUIRE(p->sh_all + 4096 <= 160 * 1024, PCNN_EINVAL, "%s: tile does not fit LDS (kernel=%d stride=%d num_classes=%d)", who, k, s, C);
   p->ws_bytes = sizeof(double) * (size_t)p->blocks * (size_t)C;   // fwd: 2 x blocks words; bwd: C x blocks (C >= 2)
   return PCNN_OK;
 }
@@ -382,14 +231,12 @@ extern "C" int pcnn_label_head_loss_fwd(const float* z, const float* bias, const
   PCNN_REQUIRE(sums, PCNN_ENULL, "%s: NULL sums", who);
   PCNN_REQUIRE(label, PCNN_ENULL, "%s: NULL label", who);
   PCNN_REQUIRE(aligned16(sums), PCNN_EINVAL, "%s: sums must be 16-byte aligned", who);
-  PCNN_REQUIRE(workspace && workspace_bytes >= p.ws_bytes, PCNN_EWORKSPACE, "%s: workspace NULL or too small (%zu < %zu bytes)",
-               who, workspace ? workspace_bytes : (size_t)0, p.ws_bytes);
-  PCNN_REQUIRE(aligned16(workspace), PCNN_EINVAL, "%s: workspace must be 16-byte aligned", who);
+  PCNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, p.ws_bytes);
   hipStream_t stream = (hipStream_t)stream_;
   double* part_s = (double*)workspace;
   long long* part_n = (long long*)workspace + p.blocks;
 #define LL_FWD(CT, CMAX)                                                                                              \
-  PCNN_LAUNCH((label_loss_fwd_kernel<CT, CMAX>), dim3((unsigned)p.blocks), dim3(LL_SEG), p.sh_fwd, stream, z, bias, gt, label, \
+  PCNN_LAUNCH((label_loss_fwd_kernel<CT, CMAX>), dim3((unsigned)p.blocks), dim3(LH_SEG), p.sh_in, stream, z, bias, gt, label, \
               terms, part_s, part_n, H, W, C, k, s, relu, p.nseg, threshold)
   if (C == 22) LL_FWD(22, 22);
   else if (C == 16) LL_FWD(16, 16);
@@ -418,13 +265,11 @@ extern "C" int pcnn_label_head_loss_bwd(const float* z, const float* bias, const
   PCNN_REQUIRE(dscore, PCNN_ENULL, "%s: NULL dscore", who);
   PCNN_REQUIRE(dbias, PCNN_ENULL, "%s: NULL dbias", who);
   PCNN_REQUIRE(aligned16(sums), PCNN_EINVAL, "%s: sums must be 16-byte aligned", who);
-  PCNN_REQUIRE(workspace && workspace_bytes >= p.ws_bytes, PCNN_EWORKSPACE, "%s: workspace NULL or too small (%zu < %zu bytes)",
-               who, workspace ? workspace_bytes : (size_t)0, p.ws_bytes);
-  PCNN_REQUIRE(aligned16(workspace), PCNN_EINVAL, "%s: workspace must be 16-byte aligned", who);
+  PCNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, p.ws_bytes);
   hipStream_t stream = (hipStream_t)stream_;
   double* part_b = (double*)workspace;
 #define LL_BWD(CT, CMAX)                                                                                              \
-  PCNN_LAUNCH((label_loss_bwd_kernel<CT, CMAX>), dim3((unsigned)p.blocks), dim3(LL_SEG), p.sh_bwd, stream, z, bias, gt, sums, \
+  PCNN_LAUNCH((label_loss_bwd_kernel<CT, CMAX>), dim3((unsigned)p.blocks), dim3(LH_SEG), p.sh_all, stream, z, bias, gt, sums, \
               upstream, dscore, part_b, H, W, C, k, s, relu, p.nseg, p.s_out_off, threshold)
   if (C == 22) LL_BWD(22, 22);
   else if (C == 16) LL_BWD(16, 16);
@@ -432,6 +277,6 @@ extern "C" int pcnn_label_head_loss_bwd(const float* z, const float* bias, const
   else if (C <= 24) LL_BWD(0, 24);
   else LL_BWD(0, 64);
 #undef LL_BWD
-  PCNN_LAUNCH(label_loss_bwd_final_kernel, dim3((unsigned)C), dim3(LL_FIN), 0, stream, part_b, (int)p.blocks, dbias);
+  PCNN_LAUNCH(channel_partials_final_kernel<CPF_THREADS>, dim3((unsigned)C), dim3(CPF_THREADS), 0, stream, part_b, (int)p.blocks, dbias);
   return check_launch(who);
 }

@@ -7,7 +7,7 @@
 //
 // Canonical reduction order (TF's reduce_sum has none): SL1_BLOCKS x 256 threads, thread (blk, t)
 // adds elements (blk*256 + t) + m*SL1_BLOCKS*256 for m ascending into f32 accumulators; a 256-leaf
-// halving tree in LDS, then a SL1_BLOCKS-leaf halving tree in a second one-block kernel. The CPU
+// halving tree in LDS (reduce_device.h), then a SL1_BLOCKS-leaf halving tree in a second one-block kernel. The CPU
 // checker restates exactly this order, so the loss matches bit for bit.
 #include "sl1_device.h"  // SL1_BLOCKS, sl1_elem, sl1_final_kernel: shared with vertex_targets.hip
 
@@ -31,14 +31,7 @@ __global__ __launch_bounds__(256) void sl1_partial_kernel(const float* __restric
   }
   sl[t] = al;
   sw[t] = aw;
-  __syncthreads();
-  for (int st = 128; st >= 1; st >>= 1) {
-    if (t < st) {
-      sl[t] = sl[t] + sl[t + st];
-      sw[t] = sw[t] + sw[t + st];
-    }
-    __syncthreads();
-  }
+  block_tree_sum<256>(sl, sw, t);
   if (t == 0) {
     partial[blockIdx.x] = sl[0];
     partial[SL1_BLOCKS + blockIdx.x] = sw[0];

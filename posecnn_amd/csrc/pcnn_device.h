@@ -44,6 +44,45 @@ void profile_end(hipStream_t stream);
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The workspace argument of the entries that take one: present, large enough, 16-byte aligned. `who` names the entry.
+#define PCNN_REQUIRE_WORKSPACE(who, ptr, have, need)                                                                    \
+  do {                                                                                                                  \
+    PCNN_REQUIRE((ptr) && (have) >= (need), PCNN_EWORKSPACE, "%s: workspace NULL or too small (%zu < %zu bytes)", (who), \
+                 (ptr) ? (size_t)(have) : (size_t)0, (size_t)(need));                                                   \
+    PCNN_REQUIRE(::pcnn::aligned16(ptr), PCNN_EINVAL, "%s: workspace must be 16-byte aligned", (who));                  \
+  } while (0)
+
+// ---- V consecutive floats as one access (V = 4: 16 bytes, the pointer 16-byte aligned; 2: 8 bytes; 1: a dword) ------------
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+template <int V>
+struct Vec;
+template <>
+struct Vec<4> { typedef float4 T; };
+template <>
+struct Vec<2> { typedef float2 T; };
+template <>
+struct Vec<1> { typedef float T; };
+
+template <int V>
+__device__ __forceinline__ void load_v(const float* p, float* r)
+{
+  typename Vec<V>::T v = *reinterpret_cast<const typename Vec<V>::T*>(p);
+  const float* f = reinterpret_cast<const float*>(&v);
+#pragma unroll
+  for (int i = 0; i < V; i++) r[i] = f[i];
+}
+template <int V>
+__device__ __forceinline__ void store_v(float* p, const float* r)
+{
+  typename Vec<V>::T v;
+  float* f = reinterpret_cast<float*>(&v);
+#pragma unroll
+  for (int i = 0; i < V; i++) f[i] = r[i];
+  *reinterpret_cast<typename Vec<V>::T*>(p) = v;
+}
+
 // ---- data exchanged between workgroups INSIDE one launch (split-K partials summed by the last workgroup) -------------
 // gfx950 has one L2 per XCD and they are only made coherent at kernel boundaries. Inside a kernel, a value another
 // XCD's workgroup must see is stored with agent scope (sc1: written through to the level all XCDs share) and loaded

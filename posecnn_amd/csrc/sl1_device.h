@@ -4,7 +4,7 @@
 // forward kernels cannot drift apart: they are held to each other bit for bit (tests/test_gpu_vertex_targets.py).
 #pragma once
 
-#include "pcnn_device.h"
+#include "reduce_device.h"
 
 namespace {
 
@@ -36,14 +36,7 @@ __global__ __launch_bounds__(SL1_BLOCKS / 2) void sl1_final_kernel(const float* 
   sl[t + SL1_BLOCKS / 2] = partial[t + SL1_BLOCKS / 2];
   sw[t] = partial[SL1_BLOCKS + t];
   sw[t + SL1_BLOCKS / 2] = partial[SL1_BLOCKS + t + SL1_BLOCKS / 2];
-  __syncthreads();
-  for (int st = SL1_BLOCKS / 2; st >= 1; st >>= 1) {
-    if (t < st) {
-      sl[t] = sl[t] + sl[t + st];
-      sw[t] = sw[t] + sw[t + st];
-    }
-    __syncthreads();
-  }
+  block_tree_sum<SL1_BLOCKS>(sl, sw, t);
   if (t == 0) {
     const float denom = sw[0] + 1e-10f;
     out[0] = div_rn(sl[0], denom);

@@ -89,14 +89,7 @@ __global__ __launch_bounds__(256) void sl1_gt_partial_kernel(const Pred pred, co
   }
   sl[t] = al;
   sw[t] = aw;
-  __syncthreads();
-  for (int st = 128; st >= 1; st >>= 1) {
-    if (t < st) {
-      sl[t] = sl[t] + sl[t + st];
-      sw[t] = sw[t] + sw[t + st];
-    }
-    __syncthreads();
-  }
+  block_tree_sum<256>(sl, sw, t);
   if (t == 0) {
     partial[blockIdx.x] = sl[0];
     partial[SL1_BLOCKS + blockIdx.x] = sw[0];

@@ -10,10 +10,10 @@
 //   pcnn_bias_relu_train_bwd         dy = gate(da) and dbias for the layers without a pool (forward: pcnn_bias_act_fwd, in place)
 //
 // All three are streams: every byte is read or written once. The bias gradient rides in the pass that writes dy: f64, fixed
-// order, no atomics — the two-stage scheme of label_loss.hip, the order stated in the header and restated in numpy by
-// tests/trunk_epilogue_ref.py.
+// order, no atomics — per-run partials here, then channel_partials_final_kernel (reduce_device.h) as in label_loss.hip; the
+// order is stated in the header and restated in numpy by tests/trunk_epilogue_ref.py. load_v / store_v: pcnn_device.h.
 #include "../../include/posecnn_hip_trunk_train.h"
-#include "pcnn_device.h"
+#include "reduce_device.h"
 
 namespace {
 
@@ -24,33 +24,6 @@ constexpr int TE_SLOTS = 16;    // pixel p of a run is summed in slot p % TE_SLO
 constexpr int TE_LANES = 16;    // threads across a workgroup's channels
 constexpr int TE_CHUNK = 64;    // channels per workgroup: TE_LANES threads x 4
 constexpr int TE_THREADS = TE_SLOTS * TE_LANES;
-constexpr int TE_FIN = 256;     // threads of the finishing kernel
-
-// as upscore.hip's load_v / store_v
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> { typedef float4 T; };
-template <>
-struct Vec<1> { typedef float T; };
-
-template <int V>
-__device__ __forceinline__ void load_v(const float* p, float* r)
-{
-  typename Vec<V>::T v = *reinterpret_cast<const typename Vec<V>::T*>(p);
-  const float* f = reinterpret_cast<const float*>(&v);
-#pragma unroll
-  for (int i = 0; i < V; i++) r[i] = f[i];
-}
-template <int V>
-__device__ __forceinline__ void store_v(float* p, const float* r)
-{
-  typename Vec<V>::T v;
-  float* f = reinterpret_cast<float*>(&v);
-#pragma unroll
-  for (int i = 0; i < V; i++) f[i] = r[i];
-  *reinterpret_cast<typename Vec<V>::T*>(p) = v;
-}
 
 // The window's byte: V of them as one word on the vector path. Written once here and read once by the backward pass, a whole
 // forward and backward of the rest of the network later: kept out of the cache lines the feature maps live in (the
@@ -282,24 +255,6 @@ __global__ __launch_bounds__(TE_THREADS) void bias_relu_pool2_train_bwd_kernel(
   if (part) te_reduce_run<V>(s_acc, acc, part, c0, C, lane, slot);
 }
 
-// one workgroup per channel
-__global__ __launch_bounds__(TE_FIN) void trunk_dbias_final_kernel(const double* __restrict__ part, int nruns,
-                                                                   float* __restrict__ dbias)
-{
-  __shared__ double s_sum[TE_FIN];
-  const int t = threadIdx.x;
-  const double* p = part + (size_t)blockIdx.x * nruns;
-  double a = 0.0;
-  for (int i = t; i < nruns; i += TE_FIN) a = a + p[i];
-  s_sum[t] = a;
-  __syncthreads();
-  for (int st = TE_FIN / 2; st >= 1; st >>= 1) {
-    if (t < st) s_sum[t] = s_sum[t] + s_sum[t + st];
-    __syncthreads();
-  }
-  if (t == 0) dbias[blockIdx.x] = (float)s_sum[0];
-}
-
 struct Plan {
   long long pixels;   // rows, or windows
   int nruns, nchunks;
@@ -330,9 +285,7 @@ int pool_plan(const char* who, int B, int H, int W, int C, Plan* p)
 int check_workspace(const char* who, const Plan& p, const float* dbias, const void* workspace, size_t workspace_bytes)
 {
   if (!dbias) return PCNN_OK;
-  PCNN_REQUIRE(workspace && workspace_bytes >= p.ws_bytes, PCNN_EWORKSPACE, "%s: workspace NULL or too small (%zu < %zu bytes)",
-               who, workspace ? workspace_bytes : (size_t)0, p.ws_bytes);
-  PCNN_REQUIRE(aligned16(workspace), PCNN_EINVAL, "%s: workspace must be 16-byte aligned", who);
+  PCNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, p.ws_bytes);
   return PCNN_OK;
 }
 
@@ -409,7 +362,7 @@ extern "C" int pcnn_bias_relu_pool2_train_bwd(const float* dpooled, const uint8_
   else
     PCNN_LAUNCH(bias_relu_pool2_train_bwd_kernel<1>, grid, dim3(TE_THREADS), 0, stream, dpooled, sel, dact, act, dy, part,
                 p.pixels, W / 2, C);
-  if (dbias) PCNN_LAUNCH(trunk_dbias_final_kernel, dim3((unsigned)C), dim3(TE_FIN), 0, stream, part, p.nruns, dbias);
+  if (dbias) PCNN_LAUNCH(channel_partials_final_kernel<CPF_THREADS>, dim3((unsigned)C), dim3(CPF_THREADS), 0, stream, part, p.nruns, dbias);
   return check_launch(who);
 }
 
@@ -434,6 +387,6 @@ extern "C" int pcnn_bias_relu_train_bwd(const float* da, const float* a, int64_t
     PCNN_LAUNCH(bias_relu_train_bwd_kernel<4>, grid, dim3(TE_THREADS), 0, stream, da, a, dy, part, (long long)rows, C, relu);
   else
     PCNN_LAUNCH(bias_relu_train_bwd_kernel<1>, grid, dim3(TE_THREADS), 0, stream, da, a, dy, part, (long long)rows, C, relu);
-  if (dbias) PCNN_LAUNCH(trunk_dbias_final_kernel, dim3((unsigned)C), dim3(TE_FIN), 0, stream, part, p.nruns, dbias);
+  if (dbias) PCNN_LAUNCH(channel_partials_final_kernel<CPF_THREADS>, dim3((unsigned)C), dim3(CPF_THREADS), 0, stream, part, p.nruns, dbias);
   return check_launch(who);
 }

@@ -17,38 +17,14 @@
 // acc = 0; for input rows ascending, input cols ascending: acc += (fy*fx) * in — products of the
 // bilinear taps are exact in f32 (multiples of 1/f^2), one rounding per multiply and per add,
 // then + add1, + add2, + bias in that order (the CPU checker restates it).
-#include "bilinear.h"
+//
+// The label head's segment, scalar per-pixel arithmetic and tile plan live in label_head_device.h, shared with the
+// training twin (label_loss.hip); load_v / store_v in pcnn_device.h, shared with trunk_epilogue.hip.
+#include "label_head_device.h"
 
 namespace {
 
 using namespace pcnn;
-
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> { typedef float4 T; };
-template <>
-struct Vec<2> { typedef float2 T; };
-template <>
-struct Vec<1> { typedef float T; };
-
-template <int V>
-__device__ __forceinline__ void load_v(const float* p, float* r)
-{
-  typename Vec<V>::T v = *reinterpret_cast<const typename Vec<V>::T*>(p);
-  const float* f = reinterpret_cast<const float*>(&v);
-#pragma unroll
-  for (int i = 0; i < V; i++) r[i] = f[i];
-}
-template <int V>
-__device__ __forceinline__ void store_v(float* p, const float* r)
-{
-  typename Vec<V>::T v;
-  float* f = reinterpret_cast<float*>(&v);
-#pragma unroll
-  for (int i = 0; i < V; i++) f[i] = r[i];
-  *reinterpret_cast<typename Vec<V>::T*>(p) = v;
-}
 
 // A workgroup owns DC_SEG consecutive output pixels of one output row (all channels): the row taps
 // are wave-uniform, the column taps sit in a small LDS table, and the npx*C output floats leave as
@@ -275,7 +251,6 @@ __global__ __launch_bounds__(256) void bias_relu_pool2_kernel(const float* __res
 // one segment's npx * C floats from LDS to a contiguous run of global memory
 __device__ __forceinline__ void up_copy_out(float* __restrict__ o, const float* s_out, int nfl, int tid, int nthreads, int seg_floats)
 {
-  typedef float v4f __attribute__((ext_vector_type(4)));
   if (((nfl | seg_floats) & 3) == 0 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
     // the segment's run of npx * C floats starts 16-byte aligned: dwordx4 stores (4x fewer store instructions)
     // Non-temporal: 432 MB per 16 frames of probabilities (and as much again of label weights) that nothing in the
@@ -307,8 +282,7 @@ __device__ __forceinline__ void up_hard_label_rows(float* s_out, const int* __re
     // the row is zeros with at most one 1: wide zero stores, then the one
     float* row = s_out + tid * C;
     if ((C & 1) == 0) {
-      typedef float f2z __attribute__((ext_vector_type(2)));
-      for (int c = 0; c < C; c += 2) *reinterpret_cast<f2z*>(row + c) = (f2z){0.f, 0.f};   // (tid * C is even)
+      for (int c = 0; c < C; c += 2) *reinterpret_cast<f2*>(row + c) = (f2){0.f, 0.f};   // (tid * C is even)
     } else {
       for (int c = 0; c < C; c++) row[c] = 0.f;
     }
@@ -321,81 +295,27 @@ __device__ __forceinline__ void up_hard_label_rows(float* s_out, const int* __re
 // Label head epilogue. A workgroup owns SEG consecutive output pixels of one output row; the
 // (<= 2) x (SEG/s + 2) low-resolution cells it needs sit in LDS; every thread owns one pixel:
 // C interpolated scores in registers -> softmax -> argmax; prob / score rows are parked in LDS and
-// leave as one contiguous run of dword stores.
-constexpr int UP_SEG = 128;
-
+// leave as one contiguous run of dword stores. Segment and arithmetic: label_head_device.h.
 template <int CMAX>
-__global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_kernel(
+__global__ __launch_bounds__(LH_SEG) void upscore_softmax_argmax_kernel(
     const float* __restrict__ z, const float* __restrict__ bias, float* __restrict__ score_out,
     float* __restrict__ prob, int* __restrict__ label, int H, int W, int C, int k, int s, int relu,
     int nseg, int s_out_off, const int* __restrict__ gt, float* __restrict__ hard, float threshold)
 {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int pad = (k - s) / 2;
-  const int Ho = H * s, Wo = W * s;
-  const int seg = blockIdx.x % nseg;
-  const int oy = (blockIdx.x / nseg) % Ho;
-  const int b = blockIdx.x / (nseg * Ho);
-  const int ox0 = seg * UP_SEG;
-  const int npx = min(UP_SEG, Wo - ox0);
+  __shared__ float s_tab[64];
   const int tid = threadIdx.x;
+  const Segment S = load_segment(z, smem, s_tab, H, W, C, k, s, nseg);   // smem: [ty.n][ncx][C]
+  float* s_out = smem + s_out_off;         // [LH_SEG][C]
+  const int npx = S.npx;
+  const long long pix0 = ((long long)S.b * H * s + S.oy) * (W * s) + S.ox0;
 
-  const Taps ty = make_taps(oy, k, s, pad, H);
-  // input columns touched by this segment
-  const Taps tfirst = make_taps(ox0, k, s, pad, W);
-  const Taps tlast = make_taps(ox0 + npx - 1, k, s, pad, W);
-  const int cx0 = tfirst.i0;
-  const int ncx = tlast.i0 + (tlast.n > 0 ? tlast.n : 1) - cx0;
-  float* s_z = smem;                       // [ty.n][ncx][C]
-  float* s_out = smem + s_out_off;         // [UP_SEG][C]
-  // a row's ncx cells x C channels are one contiguous run of z: straight copies, no index arithmetic per element
-  const int rowlen = ncx * C;
-  {
-    // four loads per thread issued before the first LDS write (see the compile-time-C kernel below)
-    const int tot = ty.n * rowlen;
-    const float* src0 = z + (((long long)b * H + ty.i0) * W + cx0) * C;
-    for (int e0 = tid; e0 < tot; e0 += 4 * UP_SEG) {
-      float v[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int e = min(e0 + j * UP_SEG, tot - 1);
-        const int ry = e / rowlen, i = e - ry * rowlen;
-        v[j] = src0[(long long)ry * W * C + i];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (e0 + j * UP_SEG < tot) s_z[e0 + j * UP_SEG] = v[j];
-    }
-  }
-  __syncthreads();
-
-  const int ox = ox0 + tid;
   float e[CMAX];
-  int best = 0;
+#pragma unroll
+  for (int c = 0; c < CMAX; c++) e[c] = 0.f;   // here, not inside interp_scores: 12 VGPRs, a wave of occupancy
   if (tid < npx) {
-    const Taps tx = make_taps(ox, k, s, pad, W);
-#pragma unroll
-    for (int c = 0; c < CMAX; c++) e[c] = 0.f;
-#pragma unroll
-    for (int jy = 0; jy < 4; jy++)
-      if (jy < ty.n) {
-#pragma unroll
-        for (int jx = 0; jx < 4; jx++)
-          if (jx < tx.n) {
-            const float w = ty.w[jy] * tx.w[jx];
-            const float* zc = s_z + (jy * ncx + (tx.i0 + jx - cx0)) * C;
-#pragma unroll
-            for (int c = 0; c < CMAX; c++)
-              if (c < C) e[c] = e[c] + w * zc[c];
-          }
-      }
-#pragma unroll
-    for (int c = 0; c < CMAX; c++)
-      if (c < C) {
-        float v = e[c] + bias[c];
-        if (relu) v = v > 0.f ? v : 0.f;
-        e[c] = v;
-      }
+    const Taps tx = make_taps_tab(S.ox0 + tid, k, s, (k - s) / 2, W, s_tab);
+    interp_scores<0, CMAX, false>(smem, bias, S.ty, tx, S.ncx, S.cx0, C, relu, e);
   }
   if (score_out) {
     if (tid < npx)
@@ -403,39 +323,19 @@ __global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_kernel(
       for (int c = 0; c < CMAX; c++)
         if (c < C) s_out[tid * C + c] = e[c];
     __syncthreads();
-    float* o = score_out + (((long long)b * Ho + oy) * Wo + ox0) * C;
-    for (int i = tid; i < npx * C; i += UP_SEG) o[i] = s_out[i];
+    float* o = score_out + pix0 * C;
+    for (int i = tid; i < npx * C; i += LH_SEG) o[i] = s_out[i];
     __syncthreads();
   }
-  if (tid < npx) {
-    // softmax_high_dimension (network.py:474-488) + argmax_2d (:432-434)
-    float m = e[0];
-#pragma unroll
-    for (int c = 0; c < CMAX; c++)
-      if (c < C) m = fmaxf(m, e[c]);
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < CMAX; c++)
-      if (c < C) { e[c] = exp_softmax_f32(e[c] - m); sum += e[c]; }
-    float bestp = div_rn(e[0], sum);
-#pragma unroll
-    for (int c = 0; c < CMAX; c++)
-      if (c < C) {
-        const float p = div_rn(e[c], sum);
-        e[c] = p;
-        if (p > bestp) { bestp = p; best = c; }
-      }
-    label[((long long)b * Ho + oy) * Wo + ox] = best;
-  }
+  if (tid < npx) label[pix0 + tid] = softmax_argmax<0, CMAX>(e, C).best;
   if (prob || hard) {
     if (tid < npx)
 #pragma unroll
       for (int c = 0; c < CMAX; c++)
         if (c < C) s_out[tid * C + c] = e[c];
     __syncthreads();
-    const long long pix0 = ((long long)b * Ho + oy) * Wo + ox0;
-    if (prob) up_copy_out(prob + pix0 * C, s_out, npx * C, tid, UP_SEG, UP_SEG * C);
-    if (hard) up_hard_label_rows(s_out, gt, hard, pix0, tid, npx, C, threshold, UP_SEG);
+    if (prob) up_copy_out(prob + pix0 * C, s_out, npx * C, tid, LH_SEG, LH_SEG * C);
+    if (hard) up_hard_label_rows(s_out, gt, hard, pix0, tid, npx, C, threshold, LH_SEG);
   }
 }
 
@@ -451,7 +351,8 @@ __global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_kernel(
 // unrolling the tap loops so that the tap arrays are not indexed dynamically: they had been living in scratch memory
 // (52 bytes per lane), a chain of private-segment loads in front of every pixel. Now 36 % of the wave cycles sit in
 // s_waitcnt and 34 % wait for issue with 5.5 waves per SIMD (LDS-limited): latency-bound at 0.25 of the HBM rate.
-typedef float f2 __attribute__((ext_vector_type(2)));
+// Its prelude is load_segment (label_head_device.h) restated with float2 copies: called through the shared function the
+// compiler schedules and allocates this kernel differently (3 instructions more), so the benchmarked kernel keeps its own.
 
 // exp_softmax_f32 (pcnn_device.h) on two values at once; branch-free: the sub-normal scaling step multiplies by 1.0f
 // where it does not apply (exact), a NaN argument is passed through by a final select
@@ -488,7 +389,7 @@ __device__ __forceinline__ f2 exp_softmax_f32x2(f2 x0)
 }
 
 template <int C>
-__global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_fixed_kernel(
+__global__ __launch_bounds__(LH_SEG) void upscore_softmax_argmax_fixed_kernel(
     const float* __restrict__ z, const float* __restrict__ bias, float* __restrict__ score_out,
     float* __restrict__ prob, int* __restrict__ label, int H, int W, int k, int s, int relu, int nseg, int s_out_off,
     const int* __restrict__ gt, float* __restrict__ hard, float threshold)
@@ -501,8 +402,8 @@ __global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_fixed_kernel(
   const int seg = blockIdx.x % nseg;
   const int oy = (blockIdx.x / nseg) % Ho;
   const int b = blockIdx.x / (nseg * Ho);
-  const int ox0 = seg * UP_SEG;
-  const int npx = min(UP_SEG, Wo - ox0);
+  const int ox0 = seg * LH_SEG;
+  const int npx = min(LH_SEG, Wo - ox0);
   const int tid = threadIdx.x;
 
   // the k tap weights once per workgroup (evaluated in double like make_deconv_filter), then integer arithmetic + lookups
@@ -515,7 +416,7 @@ __global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_fixed_kernel(
   const int cx0 = tfirst.i0;
   const int ncx = tlast.i0 + (tlast.n > 0 ? tlast.n : 1) - cx0;
   float* s_z = smem;                       // [ty.n][ncx][C]
-  float* s_out = smem + s_out_off;         // [UP_SEG][C]
+  float* s_out = smem + s_out_off;         // [LH_SEG][C]
   const int rowlen = ncx * C;              // even: copied as float2
   {
     // the segment's ty.n rows of ncx cells: FOUR loads per thread issued before the first LDS write (a row-by-row copy loop
@@ -523,17 +424,17 @@ __global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_fixed_kernel(
     const int nrow2 = rowlen / 2, tot = ty.n * nrow2;
     const float* src0 = z + (((long long)b * H + ty.i0) * W + cx0) * C;
     f2* dst = reinterpret_cast<f2*>(s_z);
-    for (int e0 = tid; e0 < tot; e0 += 4 * UP_SEG) {
+    for (int e0 = tid; e0 < tot; e0 += 4 * LH_SEG) {
       f2 v[4];
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        const int e = min(e0 + j * UP_SEG, tot - 1);
+        const int e = min(e0 + j * LH_SEG, tot - 1);
         const int ry = e / nrow2, i = e - ry * nrow2;
         v[j] = *reinterpret_cast<const f2*>(src0 + (long long)ry * W * C + 2 * i);
       }
 #pragma unroll
       for (int j = 0; j < 4; j++)
-        if (e0 + j * UP_SEG < tot) dst[e0 + j * UP_SEG] = v[j];
+        if (e0 + j * LH_SEG < tot) dst[e0 + j * LH_SEG] = v[j];
     }
   }
   __syncthreads();
@@ -578,7 +479,7 @@ __global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_fixed_kernel(
     }
     __syncthreads();
     float* o = score_out + (((long long)b * Ho + oy) * Wo + ox0) * C;
-    for (int i = tid; i < npx * C; i += UP_SEG) o[i] = s_out[i];
+    for (int i = tid; i < npx * C; i += LH_SEG) o[i] = s_out[i];
     __syncthreads();
   }
   if (tid < npx) {
@@ -611,8 +512,8 @@ __global__ __launch_bounds__(UP_SEG) void upscore_softmax_argmax_fixed_kernel(
     }
     __syncthreads();
     const long long pix0 = ((long long)b * Ho + oy) * Wo + ox0;
-    if (prob) up_copy_out(prob + pix0 * C, s_out, npx * C, tid, UP_SEG, UP_SEG * C);
-    if (hard) up_hard_label_rows(s_out, gt, hard, pix0, tid, npx, C, threshold, UP_SEG);
+    if (prob) up_copy_out(prob + pix0 * C, s_out, npx * C, tid, LH_SEG, LH_SEG * C);
+    if (hard) up_hard_label_rows(s_out, gt, hard, pix0, tid, npx, C, threshold, LH_SEG);
   }
 }
 
@@ -709,26 +610,23 @@ int upscore_softmax_argmax_impl(const char* who, const float* z, const float* bi
   PCNN_REQUIRE(k <= 64, PCNN_EINVAL, "%s: kernel size must be <= 64 (got %d)", who, k);
   PCNN_REQUIRE(z && bias && label, PCNN_ENULL, "%s: NULL pointer", who);
   hipStream_t stream = (hipStream_t)stream_;
-  const int Wo = W * s, Ho = H * s;
-  const int nseg = (Wo + UP_SEG - 1) / UP_SEG;
-  const long long blocks = (long long)B * Ho * nseg;
+  const LabelHeadPlan p = label_head_plan(B, H, W, C, k, s);
+  const int nseg = p.nseg, s_out_off = p.s_out_off;
+  const long long blocks = p.blocks;
   PCNN_REQUIRE(blocks < (1ll << 31), PCNN_EINVAL, "%s: grid too large", who);
-  const int rows = (k + s - 1) / s;                      // input rows per output row
-  const int ncx_max = (UP_SEG - 1) / s + rows + 1;       // input columns per segment
-  const int s_out_off = (rows * ncx_max * C + 3) / 4 * 4;
-  const size_t sh = sizeof(float) * ((size_t)s_out_off + (size_t)UP_SEG * C);
+  const size_t sh = p.sh_all;   // the kernels' one static array is the 256-byte tap table
   PCNN_REQUIRE(sh <= 160 * 1024, PCNN_EINVAL, "%s: tile does not fit LDS", who);
   // class counts known at compile time (even; 8-byte aligned operands): the unrolled packed-f32 kernel
   const bool al8 = ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(bias)) & 7) == 0 && s_out_off % 2 == 0;
-#define UP_FIXED(CC) PCNN_LAUNCH(upscore_softmax_argmax_fixed_kernel<CC>, dim3((unsigned)blocks), dim3(UP_SEG), sh, stream, z, bias, score_out, prob, label, H, W, k, s, relu, nseg, s_out_off, gt, hard, threshold)
+#define UP_FIXED(CC) PCNN_LAUNCH(upscore_softmax_argmax_fixed_kernel<CC>, dim3((unsigned)blocks), dim3(LH_SEG), sh, stream, z, bias, score_out, prob, label, H, W, k, s, relu, nseg, s_out_off, gt, hard, threshold)
   if (al8 && C == 22) UP_FIXED(22);
   else if (al8 && C == 14) UP_FIXED(14);
   else if (al8 && C == 16) UP_FIXED(16);
 #undef UP_FIXED
   else if (C <= 24)
-    PCNN_LAUNCH(upscore_softmax_argmax_kernel<24>, dim3((unsigned)blocks), dim3(UP_SEG), sh, stream, z, bias, score_out, prob, label, H, W, C, k, s, relu, nseg, s_out_off, gt, hard, threshold);
+    PCNN_LAUNCH(upscore_softmax_argmax_kernel<24>, dim3((unsigned)blocks), dim3(LH_SEG), sh, stream, z, bias, score_out, prob, label, H, W, C, k, s, relu, nseg, s_out_off, gt, hard, threshold);
   else
-    PCNN_LAUNCH(upscore_softmax_argmax_kernel<64>, dim3((unsigned)blocks), dim3(UP_SEG), sh, stream, z, bias, score_out, prob, label, H, W, C, k, s, relu, nseg, s_out_off, gt, hard, threshold);
+    PCNN_LAUNCH(upscore_softmax_argmax_kernel<64>, dim3((unsigned)blocks), dim3(LH_SEG), sh, stream, z, bias, score_out, prob, label, H, W, C, k, s, relu, nseg, s_out_off, gt, hard, threshold);
   return check_launch(who);
 }
 }  // namespace

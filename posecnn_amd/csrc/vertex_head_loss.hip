@@ -11,7 +11,7 @@
 //              per (cell, class present in the footprint): the k x k gather of pcnn_deconv_bilinear_bwd out of LDS,
 //              taking only the pixels of its class (the others would add +-0: the header has the argument); classes
 //              absent from the footprint are written as zeros without a walk. dbias: f64 partials of the tile's own pixels
-//              in a fixed order, then vertex_head_dbias_kernel. No floating-point atomics.
+//              in a fixed order, then channel_partials_final_kernel (reduce_device.h). No floating-point atomics.
 //
 // Measured times and what bounds them (reasoning, no counters): DESIGN.md §3.6v.
 #include "sl1_gt_device.h"
@@ -24,7 +24,6 @@ namespace {
 constexpr int VH_THREADS = 256;
 constexpr int VH_MAX_OBJECTS = 64;   // rows of a frame's table, as vertex_targets.hip
 constexpr int VH_FOOTPRINT = 3072;   // pixels of a tile's footprint kept in LDS (13 bytes each)
-constexpr int VH_FIN = 256;          // threads of the dbias kernel
 
 // element (f, y, x, ch) of deconv(z) + bias, the bits of deconv_bilinear_kernel (bilinear.h)
 struct PredLowres {
@@ -191,24 +190,6 @@ __global__ __launch_bounds__(VH_THREADS) void vertex_head_bwd_kernel(
     if (!((mask >> (c / 3)) & 1ull)) part[(size_t)c * nblk + blk] = 0.0;
 }
 
-// one workgroup per channel
-__global__ __launch_bounds__(VH_FIN) void vertex_head_dbias_kernel(const double* __restrict__ part, int nblk,
-                                                                   float* __restrict__ dbias)
-{
-  __shared__ double s_sum[VH_FIN];
-  const int t = threadIdx.x;
-  const double* p = part + (size_t)blockIdx.x * nblk;
-  double a = 0.0;
-  for (int i = t; i < nblk; i += VH_FIN) a = a + p[i];
-  s_sum[t] = a;
-  __syncthreads();
-  for (int st = VH_FIN / 2; st >= 1; st >>= 1) {
-    if (t < st) s_sum[t] = s_sum[t] + s_sum[t + st];
-    __syncthreads();
-  }
-  if (t == 0) dbias[blockIdx.x] = (float)s_sum[0];
-}
-
 struct Plan {
   int th, tw, tiles_y, tiles_x;
   long long pixels, blocks;
@@ -273,9 +254,7 @@ extern "C" int pcnn_vertex_head_loss_fwd(const float* z, const float* bias, cons
     PCNN_REQUIRE(label, PCNN_ENULL, "%s: NULL label", who);
     PCNN_REQUIRE(objects || M == 0, PCNN_ENULL, "%s: NULL objects", who);
   }
-  PCNN_REQUIRE(workspace && workspace_bytes >= p.ws_bytes, PCNN_EWORKSPACE, "%s: workspace NULL or too small (%zu < %zu bytes)",
-               who, workspace ? workspace_bytes : (size_t)0, p.ws_bytes);
-  PCNN_REQUIRE(aligned16(workspace), PCNN_EINVAL, "%s: workspace must be 16-byte aligned", who);
+  PCNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, p.ws_bytes);
   hipStream_t stream = (hipStream_t)stream_;
   float* partial = (float*)workspace;
   const int C3 = 3 * C, stride = SL1_BLOCKS * 256;
@@ -305,15 +284,13 @@ extern "C" int pcnn_vertex_head_loss_bwd(const float* z, const float* bias, cons
     PCNN_REQUIRE(dz, PCNN_ENULL, "%s: NULL dz", who);
     PCNN_REQUIRE(aligned16(dz), PCNN_EINVAL, "%s: dz must be 16-byte aligned", who);
   }
-  PCNN_REQUIRE(workspace && workspace_bytes >= p.ws_bytes, PCNN_EWORKSPACE, "%s: workspace NULL or too small (%zu < %zu bytes)",
-               who, workspace ? workspace_bytes : (size_t)0, p.ws_bytes);
-  PCNN_REQUIRE(aligned16(workspace), PCNN_EINVAL, "%s: workspace must be 16-byte aligned", who);
+  PCNN_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, p.ws_bytes);
   PCNN_REQUIRE(p.blocks < (1ll << 31), PCNN_EINVAL, "%s: grid too large", who);
   hipStream_t stream = (hipStream_t)stream_;
   double* part = (double*)workspace;
   if (p.blocks > 0)
     PCNN_LAUNCH(vertex_head_bwd_kernel, dim3((unsigned)p.blocks), dim3(VH_THREADS), p.shmem, stream, z, bias, label, instance,
                 objects, out, upstream, H, W, C, M, k, s, sigma * sigma, p.th, p.tw, p.tiles_y, p.tiles_x, dz, part);
-  PCNN_LAUNCH(vertex_head_dbias_kernel, dim3((unsigned)(3 * C)), dim3(VH_FIN), 0, stream, part, (int)p.blocks, dbias);
+  PCNN_LAUNCH(channel_partials_final_kernel<CPF_THREADS>, dim3((unsigned)(3 * C)), dim3(CPF_THREADS), 0, stream, part, (int)p.blocks, dbias);
   return check_launch(who);
 }

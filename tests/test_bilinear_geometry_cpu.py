@@ -28,13 +28,17 @@ CASE_IDS = [G.case_id(c) for c in G.cases()]
 
 
 def test_restated_constants_equal_the_kernel_sources():
-    src = {f: thresholds.parse_constants(os.path.join(thresholds.CSRC, f)) for f in ("upscore.hip", "label_loss.hip", "vertex_head_loss.hip")}
-    assert src["upscore.hip"]["UP_SEG"] == G.UP_SEG and src["label_loss.hip"]["LL_SEG"] == G.UP_SEG
+    src = {f: thresholds.parse_constants(os.path.join(thresholds.CSRC, f)) for f in ("label_head_device.h", "vertex_head_loss.hip")}
+    assert src["label_head_device.h"]["LH_SEG"] == G.UP_SEG          # the one segment length of upscore.hip and label_loss.hip
+    for f in ("upscore.hip", "label_loss.hip"):
+        text = open(os.path.join(thresholds.CSRC, f)).read()
+        assert '#include "label_head_device.h"' in text and "label_head_plan(B, H, W, C, k, s)" in text
+        assert "constexpr int UP_SEG" not in text and "constexpr int LL_SEG" not in text
     assert src["vertex_head_loss.hip"]["VH_FOOTPRINT"] == G.VH_FOOTPRINT and src["vertex_head_loss.hip"]["VH_THREADS"] == 256
     text = open(os.path.join(thresholds.CSRC, "vertex_head_loss.hip")).read()
     assert "{{4, 8}, {4, 4}, {2, 4}, {2, 2}, {1, 2}, {1, 1}}" in text and "s_row[3 * 64]" in text and "s_tap[64]" in text
     assert "sh <= 160 * 1024" in open(os.path.join(thresholds.CSRC, "upscore.hip")).read()
-    assert "p->sh_bwd + 4096 <= 160 * 1024" in open(os.path.join(thresholds.CSRC, "label_loss.hip")).read()
+    assert "p->sh_all + 4096 <= 160 * 1024" in open(os.path.join(thresholds.CSRC, "label_loss.hip")).read()
     assert VR.tile_shape(20, 10) == (4, 4) and [VR.GEOMETRY_CASES[G.vertex_name(*ks)][3:5] for ks, _ in G.VERTEX_LADDER] == [ks for ks, _ in G.VERTEX_LADDER]
 
 

@@ -84,8 +84,13 @@ def test_forward_bit_for_bit_and_loss(gpu, c, kind):
         assert float(loss) == 0.0
 
 
+# 2 x 136 rows x 1 segment = 272 workgroups: more than 256 partials per class, so the strided pass of the kernel that folds
+# them (channel_partials_final_kernel, 256 threads) takes a second trip; the generic kernel, a few KB of data
+MANY_PARTIALS = ((2, 17, 2), 5, (16, 8))
+
+
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("c", R.cases(), ids=R.case_id)
+@pytest.mark.parametrize("c", R.cases() + [MANY_PARTIALS], ids=R.case_id)
 def test_backward_kernel(gpu, c, kind):
     from posecnn_amd import ops
     shape, C, (k, s) = c
