@@ -1,6 +1,6 @@
 """ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h, include/posecnn_hip_train.h,
 include/posecnn_hip_frontend.h, include/posecnn_hip_synth.h, include/posecnn_hip_augment.h, include/posecnn_hip_loss.h,
-include/posecnn_hip_vertex_loss.h and include/posecnn_hip_trunk_train.h).
+include/posecnn_hip_vertex_loss.h, include/posecnn_hip_trunk_train.h and include/posecnn_hip_pose3d.h).
 
 This is the Python-side analogue of the reference's ``tf.load_op_library('<op>.so')`` stubs
 (lib/hough_voting_gpu_layer/hough_voting_gpu_op.py:4-7 and siblings). The library is built
@@ -172,6 +172,19 @@ TRUNK_TRAIN_SIGNATURES = {
     "pcnn_bias_relu_train_bwd": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }
 
+# the 3-D vertex route's pose entries of include/posecnn_hip_pose3d.h (same library, same ABI version)
+POSE3D_SIGNATURES = {
+    "pcnn_pose3d_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "pcnn_pose3d_prepare_fwd": (c_int, [_P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "pcnn_pose3d_sample_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_float, c_float, _P, _P, _P, _P, _P]),
+    "pcnn_pose3d_round_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                      _P, _P, _P, _P]),
+    "pcnn_pose3d_estimate_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_uint64, c_uint64, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
+                                         _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 
 def profile_enable(on=True):
     """Bracket every library kernel launch with HIP events on its launch stream."""
@@ -219,7 +232,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) +\
                 list(SYNTH_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) +\
-                list(VERTEX_LOSS_SIGNATURES.items()) + list(TRUNK_TRAIN_SIGNATURES.items()):
+                list(VERTEX_LOSS_SIGNATURES.items()) + list(TRUNK_TRAIN_SIGNATURES.items()) + list(POSE3D_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args

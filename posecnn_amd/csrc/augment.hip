@@ -21,6 +21,7 @@
 // the HLS pair with its four divisions, nine f64 operations) — at 16 x 480 x 640 about 40 us of ALU against 16 us of HBM
 // traffic: ALU bound by 2-3 x, as per-element transcendentals make a streaming kernel (DESIGN.md 3.6t has the timings).
 #include "pcnn_device.h"
+#include "philox_device.h"
 
 #include "../../include/posecnn_hip_augment.h"
 
@@ -107,35 +108,7 @@ __device__ __forceinline__ uint32_t chromatic(uint32_t q, double dh, double dl, 
   return to_byte(ob * 255.f) | (to_byte(og * 255.f) << 8) | (to_byte(orr * 255.f) << 16);
 }
 
-__device__ __forceinline__ void mulhilo(unsigned long long a, unsigned long long b, unsigned long long& hi,
-                                        unsigned long long& lo)
-{
-  hi = __umul64hi(a, b);
-  lo = a * b;
-}
-
-// Philox4x64-10, np.random.Philox's constants: the block of counter (c0, c1, c2, 0) under key (k0, k1)
-__device__ __forceinline__ void philox4x64(unsigned long long c0, unsigned long long c1, unsigned long long c2,
-                                           unsigned long long k0, unsigned long long k1, unsigned long long out[4])
-{
-  unsigned long long c3 = 0;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    unsigned long long hi0, lo0, hi1, lo1;
-    mulhilo(0xD2E7470EE14C6C93ull, c0, hi0, lo0);
-    mulhilo(0xCA5A826395121157ull, c2, hi1, lo1);
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B97F4A7C15ull;
-    k1 += 0xBB67AE8584CAA73Bull;
-  }
-  out[0] = c0;
-  out[1] = c1;
-  out[2] = c2;
-  out[3] = c3;
-}
+// philox4x64(counter, key): philox_device.h
 
 __device__ __forceinline__ float gauss_of(unsigned long long w)
 {

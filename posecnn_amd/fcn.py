@@ -16,7 +16,7 @@ from . import ops
 from .config import PIXEL_MEANS, make_meta_data
 
 __all__ = ["pad_im", "unpad_im", "nms", "_get_image_blob", "im_segment_single_frame",
-           "im_segment_batch", "combine_poses", "Detections"]
+           "im_segment_batch", "combine_poses", "Detections", "im_segment_single_frame_3d"]
 
 
 def pad_im(im, factor, value=0):
@@ -185,6 +185,70 @@ def im_segment_single_frame(net, im, im_depth, meta_data, extents, points, symme
     rois, poses_init, poses_pred = g("rois"), g("poses_init"), g("poses_tanh")
     rois, poses, _ = combine_poses(rois, poses_init, poses_pred)
     return labels_2d[0].astype(np.int32), probs[0], vertex_pred[0], rois, poses
+
+
+def _get_bb2D(extent, pose, intrinsic_matrix):
+    """lib/fcn/test.py:1115-1148: the box (x1, y1, x2, y2) of the 8 projected corners of the extent under pose
+    (quaternion wxyz, translation), float32 like the reference's arrays."""
+    from .pose_error import quat2mat
+    h = [extent[0] * 0.5, extent[1] * 0.5, extent[2] * 0.5]
+    x3d = np.ones((4, 8), dtype=np.float32)
+    for j in range(8):
+        x3d[:3, j] = [-h[0] if j & 1 else h[0], -h[1] if j & 2 else h[1], -h[2] if j & 4 else h[2]]
+    RT = np.zeros((3, 4), dtype=np.float32)
+    RT[:3, :3] = quat2mat(pose[:4])
+    RT[:, 3] = pose[4:7]
+    x2d = np.matmul(intrinsic_matrix, np.matmul(RT, x3d))
+    x2d[0, :] = np.divide(x2d[0, :], x2d[2, :])
+    x2d[1, :] = np.divide(x2d[1, :], x2d[2, :])
+    return np.array([np.min(x2d[0, :]), np.min(x2d[1, :]), np.max(x2d[0, :]), np.max(x2d[1, :])], dtype=np.float32)
+
+
+def poses_from_vertmap_3d(labels, im_depth, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None):
+    """The depth leg of lib/fcn/test.py:1353-1401 after the network: `Synthesizer.estimate_poses_3d` on the label map,
+    the depth frame and the object-coordinate field, then one row per class with poses_tmp[2, 3, j] > 0:
+    rois [n,6] = (0, class, x1, y1, x2, y2 of `_get_bb2D`), poses [n,7] = (mat2quat(R), t). The rows feed
+    `Synthesizer.icp_python(..., channel_roi=6, ...)` (:1416)."""
+    from .icp import Synthesizer, mat2quat
+    K = np.asarray(meta_data["intrinsic_matrix"], dtype=np.float64)
+    factor = float(np.asarray(meta_data["factor_depth"]).reshape(-1)[0])
+    syn = synthesizer if synthesizer is not None else Synthesizer(meshes=[], device=device)
+    extents = np.asarray(extents, dtype=np.float32)
+    poses_tmp = np.zeros((3, 4, num_classes), dtype=np.float32)
+    syn.estimate_poses_3d(labels, im_depth, vertex_pred, extents, poses_tmp, num_classes, K[0, 0], K[1, 1], K[0, 2], K[1, 2],
+                          factor, seed=seed)
+    found = [j for j in range(num_classes) if poses_tmp[2, 3, j] > 0]
+    rois = np.zeros((len(found), 6), dtype=np.float32)
+    poses = np.zeros((len(found), 7), dtype=np.float32)
+    for count, j in enumerate(found):
+        rois[count, 1] = j
+        poses[count, :4] = mat2quat(poses_tmp[:3, :3, j])
+        poses[count, 4:] = poses_tmp[:, 3, j]
+        rois[count, 2:] = _get_bb2D(extents[j, :], poses[count, :], K)
+    return rois, poses
+
+
+def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classes, seed=0, device="cuda"):
+    """lib/fcn/test.py:1353-1401 for a `vertex_reg_3d` network (lov_color_3d.yml, linemod_*_3d.yml): the graph gives
+    label_2d and the per-pixel object coordinates, `poses_from_vertmap_3d` turns them and the depth frame into poses.
+    `im` BGR uint8 and `im_depth` uint16 [H,W], padded to a multiple of 16 by the caller; meta_data needs
+    intrinsic_matrix and factor_depth. Returns (labels_2d [H,W] int32, probs [H,W,C], vertex_pred [H,W,3C], rois [n,6],
+    poses [n,7])."""
+    if not getattr(net, "vertex_reg_3d", False):
+        raise ValueError("im_segment_single_frame_3d needs a network built with vertex_reg_3d=True")
+    if net.input_format in ("DEPTH", "NORMAL"):
+        blob, data_p = _depth_frame_input(net.input_format, im_depth, meta_data, torch.device(device)), None
+    else:
+        blob, blob_depth, _ = _get_image_blob(im, im_depth)
+        data_p = blob_depth if net.input_format == "RGBD" else None
+    K = np.array(meta_data["intrinsic_matrix"], dtype=np.float64)
+    none = np.zeros((num_classes, 1, 3), dtype=np.float32)           # points / symmetry: no layer of this graph reads them
+    feed = _feed(net, blob, data_p, K, extents, none, np.zeros((num_classes,), dtype=np.float32), num_classes, torch.device(device))
+    net.run(feed)
+    g = lambda n: net.get_output(n).detach().cpu().numpy()
+    labels_2d, probs, vertex_pred = g("label_2d")[0].astype(np.int32), g("prob_normalized")[0], g("vertex_pred")[0]
+    rois, poses = poses_from_vertmap_3d(labels_2d, im_depth, vertex_pred, meta_data, extents, num_classes, seed, device)
+    return labels_2d, probs, vertex_pred, rois, poses
 
 
 class Detections(object):

@@ -378,6 +378,25 @@ class Synthesizer:
             t = T[:, 3].astype(np.float32)
             centers[m] = (np.float32(fx) * (t[0] / t[2]) + np.float32(px), np.float32(fy) * (t[1] / t[2]) + np.float32(py))
 
+    def estimate_poses_3d(self, labels, depth, vertmap, extents, poses, num_classes, fx, fy, px, py, factor, seed=0):
+        """`Synthesizer.estimate_poses_3d` (synthesizer.pyx:86-95 -> estimatePose3D, synthesize.cpp:1769-1966) with the
+        reference's arguments: labels int32 [H,W], depth uint16 [H,W], vertmap f32 [H,W,3 num_classes] (the network's
+        `vertex_pred`), extents f32 [num_classes,3]; poses f32 [3,4,num_classes] is filled in place — R|t of class j in
+        poses[:, :, j], left as it was for a class without a pose (the caller reads poses[2, 3, j] > 0 as found).
+        One frame through ops.estimate_poses_3d; `seed` keys its sampler."""
+        from . import ops
+        dev = self.device
+        labels_t = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)[None]).to(dev)
+        depth_t = torch.from_numpy(np.ascontiguousarray(depth, dtype=np.uint16)[None]).to(dev)
+        vert_t = torch.from_numpy(np.ascontiguousarray(vertmap, dtype=np.float32)[None]).to(dev)
+        ext_t = torch.from_numpy(np.ascontiguousarray(extents, dtype=np.float32).reshape(int(num_classes), 3)).to(dev)
+        intr = torch.tensor([[fx, fy, px, py]], dtype=torch.float32, device=dev)
+        out, _, _, _, num_hyps = ops.estimate_poses_3d(labels_t, depth_t, vert_t, ext_t, intr, float(factor), seed=seed)
+        out, found = out[0].cpu().numpy(), num_hyps[0].cpu().numpy() > 0
+        for j in range(int(num_classes)):
+            if found[j]:
+                poses[:, :, j] = out[j]
+
     def icp_python(self, labelmap, depth, parameters, height, width, num_roi, channel_roi, rois, poses, outputs, outputs_icp,
                    maxError, iterations=8, min_pixels=400, radius=0.01):
         """`Synthesizer::icp_python` -> `solveICP`. parameters = (fx, fy, px, py, znear, zfar, factor_depth);

@@ -26,6 +26,7 @@ __all__ = [
     "depth_normals", "bilateral_filter_u8", "normal_image", "bilateral_tables", "augment_frames",
     "label_head_loss", "label_head_loss_grad", "vertex_head_loss", "vertex_head_loss_grad",
     "bias_relu_train_", "bias_relu_train_grad", "bias_relu_pool2_train", "bias_relu_pool2_train_grad",
+    "estimate_poses_3d", "pose3d_prepare", "pose3d_sample", "pose3d_round",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1629,3 +1630,163 @@ def augment_frames(color, depth=None, params=None, seed=0, pixel_means=None, dep
                                         seed & (1 << 64) - 1, seed >> 64, norm, B, H, W, _ptr(data), _ptr(data_p), _ptr(ws),
                                         nbytes.value, _stream(data)))
     return data, data_p
+
+
+# ------------------------------------------------------------------------------------------------
+# 3-D vertex route: preemptive RANSAC + Kabsch poses from object coordinates (include/posecnn_hip_pose3d.h)
+POSE3D_DEFAULTS = dict(hypotheses=256, pixel_batch=1000, max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=0.01,
+                       min_dist=0.01, min_pixels=10, max_attempts=1024)   # synthesize.cpp:1783-1799; max_attempts is ours
+
+
+def _pose3d_frames(label_2d, depth, vertex_pred, extents, intrinsics):
+    label_2d = _dev(label_2d, "label_2d", torch.int32)
+    depth = _dev(depth, "depth", torch.uint16)
+    if depth.dim() == 4 and depth.shape[3] == 1:
+        depth = depth.reshape(depth.shape[:3])
+    vertex_pred = _dev(vertex_pred, "vertex_pred", torch.float32)
+    extents = _dev(extents, "extents", torch.float32)
+    intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+    if label_2d.dim() != 3:
+        raise ValueError("label_2d must be [B,H,W] (got %s)" % (tuple(label_2d.shape),))
+    B, H, W = label_2d.shape
+    if tuple(depth.shape) != (B, H, W):
+        raise ValueError("depth must be uint16 [%d,%d,%d] (got %s)" % (B, H, W, tuple(depth.shape)))
+    if extents.dim() != 2 or extents.shape[1] != 3:
+        raise ValueError("extents must be [C,3] (got %s)" % (tuple(extents.shape),))
+    C = extents.shape[0]
+    if tuple(vertex_pred.shape) != (B, H, W, 3 * C):
+        raise ValueError("vertex_pred must be [%d,%d,%d,%d] (got %s)" % (B, H, W, 3 * C, tuple(vertex_pred.shape)))
+    if tuple(intrinsics.shape) != (B, 4):
+        raise ValueError("intrinsics must be [B,4] rows (fx, fy, px, py) with B = %d (got %s)" % (B, tuple(intrinsics.shape)))
+    return label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C
+
+
+def _pose3d_streams(streams, B, device):
+    if streams is None:
+        return torch.zeros((B,), dtype=torch.int64, device=device)
+    if not isinstance(streams, torch.Tensor):
+        ids = [int(v) for v in streams]
+        if any(not 0 <= v < 1 << 64 for v in ids):
+            raise ValueError("streams must be in [0, 2^64)")
+        streams = torch.from_numpy(np.array(ids, dtype=np.uint64).view(np.int64)).to(device)
+    streams = _dev(streams, "streams", torch.int64)
+    if tuple(streams.shape) != (B,):
+        raise ValueError("streams must be one id per frame, [%d] (got %s)" % (B, tuple(streams.shape)))
+    return streams
+
+
+def _pose3d_seed(seed):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 128:
+        raise ValueError("seed must be in [0, 2^128)")
+    return seed & (1 << 64) - 1, seed >> 64
+
+
+def pose3d_prepare(label_2d, depth, vertex_pred, extents, intrinsics, factor_depth):
+    """The correspondence records of `estimate_poses_3d` (getEye, getLabels, getMode3D): -> (records f32 [B,H*W,6] rows
+    (eye xyz, obj xyz), compacted per (frame, class) in raster order, counts int32 [B,C], offsets int32 [B,C]). Rows past a
+    frame's total are not written."""
+    label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C = _pose3d_frames(label_2d, depth, vertex_pred, extents, intrinsics)
+    dev = label_2d.device
+    records = torch.empty((B, H * W, 6), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, C), dtype=torch.int32, device=dev)
+    offsets = torch.empty((B, C), dtype=torch.int32, device=dev)
+    check("pcnn_pose3d_prepare_fwd",
+          lib().pcnn_pose3d_prepare_fwd(_ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics),
+                                        float(factor_depth), B, H, W, C, _ptr(records), _ptr(counts), _ptr(offsets),
+                                        _stream(records)))
+    return records, counts, offsets
+
+
+def _pose3d_records(records, counts, offsets, H, W):
+    records = _dev(records, "records", torch.float32)
+    counts = _dev(counts, "counts", torch.int32)
+    offsets = _dev(offsets, "offsets", torch.int32)
+    if records.dim() != 3 or records.shape[1] != H * W or records.shape[2] != 6:
+        raise ValueError("records must be [B,%d,6] (got %s)" % (H * W, tuple(records.shape)))
+    B = records.shape[0]
+    if counts.dim() != 2 or counts.shape[0] != B or counts.shape != offsets.shape:
+        raise ValueError("counts and offsets must be [B,C] (got %s, %s)" % (tuple(counts.shape), tuple(offsets.shape)))
+    return records, counts, offsets, B, counts.shape[1]
+
+
+def pose3d_sample(records, counts, offsets, extents, intrinsics, height, width, seed=0, streams=None, hypotheses=256,
+                  max_attempts=1024, min_area=400, inlier_threshold=0.01, min_dist=0.01):
+    """One 3-point hypothesis per (frame, h) from `pose3d_prepare`'s records: -> (hyp_pose f64 [B,hypotheses,3,4],
+    hyp_class int32 [B,hypotheses] (0: none found), hyp_attempt int32 (the accepted attempt, -1), hyp_rec int32 [..,3]
+    (the three records, indices inside their class))."""
+    H, W = int(height), int(width)
+    records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
+    extents = _dev(extents, "extents", torch.float32)
+    intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+    if tuple(extents.shape) != (C, 3) or tuple(intrinsics.shape) != (B, 4):
+        raise ValueError("extents must be [%d,3] and intrinsics [%d,4]" % (C, B))
+    dev = records.device
+    streams = _pose3d_streams(streams, B, dev)
+    s0, s1 = _pose3d_seed(seed)
+    n = int(hypotheses)
+    hyp_pose = torch.empty((B, max(n, 0), 3, 4), dtype=torch.float64, device=dev)
+    hyp_class = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
+    hyp_attempt = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
+    hyp_rec = torch.empty((B, max(n, 0), 3), dtype=torch.int32, device=dev)
+    check("pcnn_pose3d_sample_fwd",
+          lib().pcnn_pose3d_sample_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(extents), _ptr(intrinsics), _ptr(streams),
+                                       s0, s1, B, H, W, C, n, int(max_attempts), int(min_area), float(inlier_threshold),
+                                       float(min_dist), _ptr(hyp_pose), _ptr(hyp_class), _ptr(hyp_attempt), _ptr(hyp_rec),
+                                       _stream(records)))
+    return hyp_pose, hyp_class, hyp_attempt, hyp_rec
+
+
+def pose3d_round(records, counts, offsets, hyp_pose, hyp_class, height, width, round, pixel_batch=1000, max_pixels=1000,
+                 inlier_threshold=0.01):
+    """ONE count -> rank -> halve -> refit round of the preemptive loop on the given hypotheses (hyp_class 0: empty slot):
+    -> (pose_out f64 [B,n,3,4], class_out int32 [B,n] (0 where the slot was dropped), inliers_out int32 [B,n])."""
+    H, W = int(height), int(width)
+    records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
+    hyp_pose = _dev(hyp_pose, "hyp_pose", torch.float64)
+    hyp_class = _dev(hyp_class, "hyp_class", torch.int32)
+    if hyp_class.dim() != 2 or hyp_class.shape[0] != B or tuple(hyp_pose.shape) != tuple(hyp_class.shape) + (3, 4):
+        raise ValueError("hyp_class must be [B,n] and hyp_pose [B,n,3,4] (got %s, %s)" % (tuple(hyp_class.shape), tuple(hyp_pose.shape)))
+    n = hyp_class.shape[1]
+    dev = records.device
+    pose_out = torch.empty((B, n, 3, 4), dtype=torch.float64, device=dev)
+    class_out = torch.empty((B, n), dtype=torch.int32, device=dev)
+    inliers_out = torch.empty((B, n), dtype=torch.int32, device=dev)
+    check("pcnn_pose3d_round_fwd",
+          lib().pcnn_pose3d_round_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(hyp_pose), _ptr(hyp_class), B, H, W, C, n,
+                                      int(round), int(pixel_batch), int(max_pixels), float(inlier_threshold), _ptr(pose_out),
+                                      _ptr(class_out), _ptr(inliers_out), _stream(records)))
+    return pose_out, class_out, inliers_out
+
+
+def estimate_poses_3d(label_2d, depth, vertex_pred, extents, intrinsics, factor_depth, seed=0, streams=None, hypotheses=256,
+                      pixel_batch=1000, max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=0.01, min_dist=0.01,
+                      min_pixels=10, max_attempts=1024, workspace=None):
+    """`Synthesizer::estimatePose3D` (lib/synthesize/synthesize.cpp:1769-1966) for a batch, three launches and no
+    synchronisation: label_2d int32 [B,H,W], depth uint16 [B,H,W], vertex_pred f32 [B,H,W,3C] (the `vertex_reg_3d` network's
+    object coordinates, scaled into [0, 1] per extent), extents f32 [C,3], intrinsics f32 [B,4] rows (fx, fy, px, py).
+    seed: the Philox key (< 2^128); streams: one uint64 id per frame (default 0), so that a frame's poses do not depend on
+    its batch slot. min_pixels only gated the reference's nlopt polish, which is not built: accepted and unused.
+    Returns device tensors (poses f32 [B,C,3,4], poses64 f64 [B,C,3,4], inliers, ref_steps, num_hyps int32 [B,C]); a class
+    without hypothesis is all zero (the reference's caller reads t_z > 0 as found). Deviations from the reference:
+    DESIGN.md 3.7b."""
+    label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C = _pose3d_frames(label_2d, depth, vertex_pred, extents, intrinsics)
+    dev = label_2d.device
+    streams = _pose3d_streams(streams, B, dev)
+    s0, s1 = _pose3d_seed(seed)
+    int(min_pixels)
+    nbytes = c_size_t()
+    check("pcnn_pose3d_workspace_bytes", lib().pcnn_pose3d_workspace_bytes(B, H, W, C, int(hypotheses), ctypes.byref(nbytes)))
+    ws = (workspace or _ws(dev, "pose3d")).get(nbytes.value, dev)
+    poses64 = torch.empty((B, C, 3, 4), dtype=torch.float64, device=dev)
+    poses = torch.empty((B, C, 3, 4), dtype=torch.float32, device=dev)
+    inliers = torch.empty((B, C), dtype=torch.int32, device=dev)
+    ref_steps = torch.empty((B, C), dtype=torch.int32, device=dev)
+    num_hyps = torch.empty((B, C), dtype=torch.int32, device=dev)
+    check("pcnn_pose3d_estimate_fwd",
+          lib().pcnn_pose3d_estimate_fwd(_ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics),
+                                         _ptr(streams), float(factor_depth), s0, s1, B, H, W, C, int(hypotheses), int(pixel_batch),
+                                         int(max_pixels), int(ref_it), int(min_area), float(inlier_threshold), float(min_dist),
+                                         int(max_attempts), _ptr(poses64), _ptr(poses), _ptr(inliers), _ptr(ref_steps),
+                                         _ptr(num_hyps), _ptr(ws), nbytes.value, _stream(poses)))
+    return poses, poses64, inliers, ref_steps, num_hyps
