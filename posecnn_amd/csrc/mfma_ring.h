@@ -19,6 +19,13 @@
 //   * The ring position travels in the offset field of the reads (one copy of a half stage's six reads per buffer behind
 //     a scalar branch): a lane's chunk addresses are loop invariants and a stage has no vector-ALU instruction between its
 //     MFMAs — on gfx950 a VALU instruction is never hidden behind an MFMA of its SIMD.
+//   * An operand that only its own wave reads need not pass through the ring at all (wino_mfma.hip, BSRC = 1: a wave's 16
+//     filter rows). It comes by RING_GLOAD_B128 straight into registers, one stage ahead, and its loads sit in the SAME vmcnt
+//     queue as the DMAs, in issue order. So the order of issue inside a stage is part of the protocol: the register loads
+//     of stage s+1 go out BEFORE the DMAs of stage s+2, and N of the counted wait stays the DMA instructions per stage —
+//     everything older than the youngest stage's DMAs, this stage's registers included, has then landed. A register with
+//     a load in flight is not read, moved or reused before that wait: the compiler does not know the load is pending, so
+//     this is checked in the ISA (roles of the register sets fixed at compile time; no copy of them in the loop).
 #pragma once
 
 namespace pcnn {
@@ -45,3 +52,9 @@ __device__ __forceinline__ unsigned ring_chunk_bytes(int j, int lk, int lr) { re
 
 // the ring position OFF (a compile-time constant) is part of the instruction, not of the address
 #define RING_DSREAD_B128(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "i"(OFF))
+
+// 16 bytes per lane, global -> registers, beside the DMAs and in their vmcnt queue: SGPR base + 32-bit VGPR byte offset
+// + a compile-time offset (13 bits, signed). DST must not be read, moved or reused before the hand-placed vmcnt wait
+// that covers it.
+#define RING_GLOAD_B128(DST, SBASE, VOFF, OFF) \
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(DST) : "v"(VOFF), "s"(SBASE), "i"(OFF) : "memory")

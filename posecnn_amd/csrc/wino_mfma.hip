@@ -31,6 +31,13 @@
 //    lane's 8 read addresses are loop invariants: the ring position travels in the reads' offset field
 //    (three copies of a half stage's six reads behind a scalar branch), so a stage has NO vector-ALU
 //    instruction between its 32 MFMAs.
+//  * The packed route (BSRC = 1, pcnn_winograd43_conv_packed_fwd): wave w is the only reader of U^T rows 16 w ... 16 w + 15
+//    (it issues exactly the DMAs of the rows it later reads), so the filter operand needs neither LDS nor the barrier. It
+//    comes by global_load_dwordx4 straight into registers, one stage ahead, from a fragment-major bank built once per
+//    filter (wino43_pack_filters_kernel: one wave-wide load = one contiguous KB). Per wave and stage 2 DMA instructions
+//    instead of 6, 8 ds_read_b128 instead of 12, a ring of 24 KB instead of 72 (the kernel's 64 KB are the epilogue's
+//    staging buffers); four B register sets whose roles alternate from stage to stage, statically (the K loop walks
+//    stage pairs). Same products, same K order, same fold — the same bits; BSRC = 0 is the kernel as it was.
 //  * Epilogue: bias + ReLU (+ 2x2 max-pool of the 4x4 tile) in registers, then through LDS (two staging
 //    buffers, one barrier per pass) so that every store instruction writes whole 256-byte channel rows
 //    (the C/D layout alone would give 64-byte segments).
@@ -46,6 +53,7 @@
 
 #include "pcnn_device.h"
 #include "mfma_ring.h"
+#include "../../include/posecnn_hip_wino_packed.h"
 
 namespace {
 
@@ -72,9 +80,17 @@ enum : int {
   ABL_NO_STORES = 128,      // unpooled output (POOL 0 / 2): the staged rows are read back but not stored
   ABL_EPI_REGS_ONLY = 256,  // epilogue = bias + ReLU on the registers, nothing staged or stored
   ABL_NT_STORES = 512,      // unpooled output: non-temporal stores
+  ABL_NO_B_LOADS = 1024,    // BSRC = 1: no filter loads into registers (the operand registers stay what they are)
 };
 
 // POOL: 0 = y [.,H,W,Cout]; 1 = only max_pool_2x2(y) (written to y); 2 = both (y and ypool)
+// BSRC: where the filter operand B (the wave's 16 U^T rows) comes from. 0 = through the LDS ring like A, from the row-major
+// bank ut [group][36][Cout][Cin]. 1 = straight from global memory into registers, from the fragment-major bank utp of
+// wino43_pack_filters_kernel below: no wave reads a B row that another wave brought in, so B needs neither LDS nor the
+// stage barrier. The ring then holds A alone (24 KB; the 64 KB of the kernel are the epilogue's staging buffers), a wave
+// issues 2 DMA instructions per stage instead of 6 and 8 ds_read_b128 instead of 12. Same products, same K order
+// (k = 16 j + 4 lk + i), same accumulator chains: the same bits.
+// ODD (BSRC = 1 only): the parity of the K stages per plane, NK — the launcher's business; see the plane loops.
 // ABL: see above.
 // `mode` bit 0: XCD x owns channel block x (launches with ncb == 8 whose filter bank outweighs their transformed input,
 // i.e. the deep layers of a single frame: every XCD then streams ITS eighth of U once instead of all of U).
@@ -95,14 +111,14 @@ enum : int {
 //     ablation had priced the staging at 7 / 5 / 4 % of conv2_1 / conv2_2 / conv3_2; the direct form gives it back in
 //     64-byte partial-line stores: 12 layers 14.136 against 14.169 ms alone, inside the step 1107 / 1118 against 1098 /
 //     1098 us per launch, the step 796 / 794 against 764 / 808 frames/s. No gain: the staged epilogue stays.
-template <int POOL, int ABL = 0>
+template <int POOL, int BSRC = 0, int ABL = 0, int ODD = 0>
 __global__ __launch_bounds__(64 * WM_NW, 2) void wino43_mfma_kernel(
     const float* __restrict__ v, const float* __restrict__ ut, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ ypool, int H, int W, int Cin, int Cout, int Ht, int Wt,
     long long T, long long tiles_per_group, int relu, int nbt, int ncb, int ksplit, long long ysplit_stride, int mode)
 {
-  constexpr int RING = WM_NBUF * (WM_BT + 64) * WM_LD, STAGE2 = 2 * WM_BT * 4 * 64;
-  __shared__ __attribute__((aligned(16))) float smem[RING > STAGE2 ? RING : STAGE2];   // sA[3][WM_BT][64] | sB[3][64][64]; epilogue: 2 x [WM_BT][4][64]
+  constexpr int RING = WM_NBUF * (WM_BT + (BSRC == 0 ? 64 : 0)) * WM_LD, STAGE2 = 2 * WM_BT * 4 * 64;
+  __shared__ __attribute__((aligned(16))) float smem[RING > STAGE2 ? RING : STAGE2];   // sA[3][WM_BT][64] | BSRC 0: sB[3][64][64]; epilogue: 2 x [WM_BT][4][64]
 
   // XCD-aware block map: XCD x = blockIdx % 8 takes tile blocks tb == x (mod 8); on an XCD the
   // channel blocks of a tile block are consecutive
@@ -180,8 +196,10 @@ __global__ __launch_bounds__(64 * WM_NW, 2) void wino43_mfma_kernel(
     const unsigned lb_ = lds_b0 + (unsigned)(BUF) * (64 * WM_LD * 4);          \
     glds16_s(vs_, va0, la_);                                                 \
     glds16_s(vs_, va1, la_ + 4 * WM_LD * 4);                                 \
-    _Pragma("unroll") for (int i_ = 0; i_ < WM_UB; i_++)                      \
-      glds16_s(us_, ub[i_], lb_ + 4 * i_ * WM_LD * 4);                        \
+    if constexpr (BSRC == 0) {                                               \
+      _Pragma("unroll") for (int i_ = 0; i_ < WM_UB; i_++)                    \
+        glds16_s(us_, ub[i_], lb_ + 4 * i_ * WM_LD * 4);                      \
+    }                                                                        \
   }
 
   // Stage order: nu outer, xi, then kc fastest; (pnu, pxi, pkc) is the prefetch pointer, two stages
@@ -189,22 +207,55 @@ __global__ __launch_bounds__(64 * WM_NW, 2) void wino43_mfma_kernel(
   // The prefetch offsets (floats) advance incrementally on the scalar unit: next K slice +64; next
   // plane of the column k += 6; next column k: 30 + nu -> nu + 1.
   int pnu = 0, pxi = 0, pkc = 0;
-  long long pvo = (long long)ks * NK * WM_KC, puo = pvo;   // this split's first input channel
-  const long long kback = (long long)(NK - 1) * WM_KC;
+  // BSRC = 1: a stage of the packed bank is the wave's own 4 KB [4 (K group j)][64 lanes][4] at
+  // ((16-channel block) * Cin / 64 + K slice) * 1024 floats of its plane; planes are Cout * Cin floats apart as in ut
+  constexpr int WM_USTEP = BSRC == 0 ? WM_KC : 16 * WM_KC;   // floats from one K slice of B to the next
+  long long pvo = (long long)ks * NK * WM_KC;   // this split's first input channel
+  long long puo = BSRC == 0 ? pvo : ((long long)(cb_data * (WM_BC / 16) + wave) * (Cin / WM_KC) + (long long)ks * NK) * WM_USTEP;
+  const long long kback = (long long)(NK - 1) * WM_KC, ukback = (long long)(NK - 1) * WM_USTEP;
   // uniform branches on the scalar unit (3-4 SALU instructions on the common path; a select-only
   // version cost ~40 per stage and measured 1.2 % slower over the 12 layers); past the last stage the
   // pointer parks on it (the two extra prefetches re-load the last stage into a free buffer and are
   // drained before the epilogue)
-  const long long dvx = 6 * vplane - kback, dux = 6 * uplane - kback;       // next plane of the column
-  const long long dvn = -29 * vplane - kback, dun = -29 * uplane - kback;   // next column
+  const long long dvx = 6 * vplane - kback, dux = 6 * uplane - ukback;       // next plane of the column
+  const long long dvn = -29 * vplane - kback, dun = -29 * uplane - ukback;   // next column
 #define WM_PF_ADVANCE()                                                                          \
   do {                                                                                           \
-    if (pkc + 1 < NK) { pkc++; pvo += WM_KC; puo += WM_KC; }            /* next K slice */        \
+    if (pkc + 1 < NK) { pkc++; pvo += WM_KC; puo += WM_USTEP; }         /* next K slice */        \
     else if (pxi < 5) { pkc = 0; pxi++; pvo += dvx; puo += dux; }       /* next plane of the column */ \
     else if (pnu < 5) { pkc = 0; pxi = 0; pnu++; pvo += dvn; puo += dun; }   /* next column */     \
   } while (0)   /* past the last stage the pointer parks on it */
-  { WM_DMA(0, pvo, puo); WM_PF_ADVANCE(); }
-  { WM_DMA(1, pvo, puo); WM_PF_ADVANCE(); }
+  // BSRC = 1: the filter operand lives in four register sets of two K groups each. A stage uses a pair (groups 0, 1 |
+  // groups 2, 3) while the other pair receives the NEXT stage's — B runs one stage ahead, A two —, and the pairs swap
+  // roles every stage — statically: the stage's parity is a macro argument and the K loop walks stage pairs (see the
+  // stage below; a register copy instead would be 16 VALU instructions between the stage's MFMAs).
+  // The loads are inline asm like the DMAs, whose vmcnt they share: a compiler-visible load among DMAs it cannot see
+  // would get a wait that is too lax. SGPR base (advanced like pvo) + one loop-invariant lane offset; the K group
+  // travels in the offset field.
+  v4f bq[4][2];
+  if constexpr (BSRC == 1 && (ABL & ABL_NO_B_LOADS)) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) bq[i][0] = bq[i][1] = (v4f){1.f, 1.f, 1.f, 1.f};
+  }
+  const unsigned vbo = 16u * (unsigned)lane;
+  long long pub = 0;   // B's own prefetch offset: the stage behind (pvo, puo)
+#define WM_BLOAD(S, UO, J0)                                                  \
+  if constexpr (!(ABL & ABL_NO_B_LOADS)) {                                   \
+    const char* us_ = ubase + (UO) * 4;                                      \
+    RING_GLOAD_B128(S[0], us_, vbo, (J0) * 1024);                            \
+    RING_GLOAD_B128(S[1], us_, vbo, (J0) * 1024 + 1024);                     \
+  }
+  if constexpr (BSRC == 0) {
+    { WM_DMA(0, pvo, puo); WM_PF_ADVANCE(); }
+    { WM_DMA(1, pvo, puo); WM_PF_ADVANCE(); }
+  } else {
+    // B of stage 0, then A of stages 0 and 1: at every stage barrier the two youngest entries of the wave's vmcnt queue
+    // are the A DMAs of the stage after, everything older (this stage's A and B) has landed behind vmcnt(2)
+    WM_BLOAD(bq[0], puo, 0);
+    WM_BLOAD(bq[1], puo, 2);
+    { WM_DMA(0, pvo, puo); WM_PF_ADVANCE(); }
+    { WM_DMA(1, pvo, puo); pub = puo; WM_PF_ADVANCE(); }
+  }
   int cur = 0;
 
   // ds_read side of the swizzle: row R = (..) + lr, logical chunk 4 j + lk -> physical (4 j + lk) ^ lr
@@ -249,6 +300,17 @@ __global__ __launch_bounds__(64 * WM_NW, 2) void wino43_mfma_kernel(
   else if (cur == 0) { WM_READ_AT(SA0, SA1, SB, G0, 0); }                                             \
   else if (cur == 1) { WM_READ_AT(SA0, SA1, SB, G0, 1); }                                             \
   else { WM_READ_AT(SA0, SA1, SB, G0, 2); }
+  // BSRC = 1: the A reads alone (four per half stage)
+#define WM_READA_AT(SA0, SA1, G0, CUR)                                                                \
+  _Pragma("unroll") for (int g_ = 0; g_ < 2; g_++) {                                                  \
+    WM_DSREAD(SA0[g_], adA[(G0) + g_], (CUR) * (WM_BT * WM_LD * 4));                                  \
+    WM_DSREAD(SA1[g_], adA[(G0) + g_], (CUR) * (WM_BT * WM_LD * 4) + 4096);                           \
+  }
+#define WM_READA(SA0, SA1, G0)                                                                        \
+  if constexpr (ABL & ABL_NO_LDS_READS) { WM_READA_AT(SA0, SA1, G0, 0); }                             \
+  else if (cur == 0) { WM_READA_AT(SA0, SA1, G0, 0); }                                                \
+  else if (cur == 1) { WM_READA_AT(SA0, SA1, G0, 1); }                                                \
+  else { WM_READA_AT(SA0, SA1, G0, 2); }
   static_assert(WM_NBUF == 3, "WM_READ dispatches over a ring of three buffers");
 #define WM_MFMA1(SA0, SA1, SB, G, ACC)                                                                \
   if constexpr (ABL & ABL_NO_MFMA) { asm volatile("" :: "v"(SA0[G]), "v"(SA1[G]), "v"(SB[G])); } else \
@@ -307,7 +369,7 @@ __global__ __launch_bounds__(64 * WM_NW, 2) void wino43_mfma_kernel(
   //   buffer the previous stage just freed -> reads X(s) -> MFMAs Y(s-1) -> reads Y(s) -> MFMAs X(s)
   // vmcnt(6): the 2 + WM_UB DMA instructions of the NEXT stage are what may still be in flight. (ABL_NO_BARRIER waits
   // on a stricter vmcnt(4): every record of that ablation was measured with it.)
-#define WM_STAGE(XI, XP)                                                                              \
+#define WM_STAGE0(XI, XP)                                                                             \
   do {                                                                                                \
     if constexpr (ABL & ABL_NO_BARRIER) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");   \
     else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");                     \
@@ -336,30 +398,117 @@ __global__ __launch_bounds__(64 * WM_NW, 2) void wino43_mfma_kernel(
   } while (0)
   static_assert(2 + WM_UB == 6, "the stage barrier's vmcnt(6) counts the 2 + WM_UB DMA instructions a wave issues per stage");
 
+  // The same stage with B in registers (BSRC = 1), at stage parity P: this stage's K groups 0, 1 are in bq[2 P], its groups
+  // 2, 3 in bq[2 P + 1] (the NEXT stage reads them, behind its barrier); the next stage's B goes to bq[2 - 2 P] and
+  // bq[3 - 2 P]. The latter still holds groups 2, 3 of the stage before and is free once the MFMAs of Y(s-1) have been
+  // issued; the former has been free since the end of the stage before, so its loads go out first, right behind the barrier.
+  // Every stage — a plane's or a column's first, and the parked ones past the last — issues, in this order, 4 B loads of
+  // stage s+1 and then 2 A DMAs of stage s+2. At the barrier of stage s the wave's queue therefore holds, oldest first,
+  // A(s) (issued in s-2), B(s) and A(s+1) (both in s-1): vmcnt(2) leaves the two A DMAs of the next stage in flight and
+  // retires everything older, this stage's B included. Loads and DMAs return in issue order.
+  constexpr int WM_VM1 = WM_BT / 4 / WM_NW;   // A DMA instructions per wave and stage
+  // The roles of the four register sets are STATIC: stage parity P (0: this stage's B in bq[0] | bq[1], the next stage's
+  // into bq[2] | bq[3]; 1: the other way round) is a macro argument, and the K loop of a plane walks its stages in pairs.
+  // A column has 6 NK stages, an even number, so every column starts at parity 0; a plane starts at parity 0 when NK is
+  // even or the plane index is, at parity 1 otherwise — two forms of the column loop, chosen by the template parameter ODD
+  // (both in one kernel behind a test of NK's low bit cost the register allocator 4 registers more than there are).
+  // (Parity as a run-time value — two copies of the stage, or of every statement that names a B register, behind a scalar
+  // branch — made the compiler hoist the fold in front of the branch or sink it behind the loads and copy register sets
+  // where the copies meet: 200-400 registers spilled.)
+#define WM_YMFMA_R(SB, ACC)                                                                           \
+  __builtin_amdgcn_sched_barrier(0); WM_MFMA(ya0, ya1, SB, ACC); __builtin_amdgcn_sched_barrier(0)
+#define WM_STAGE1(XI, XP, P, KC)                                                                      \
+  do {                                                                                                \
+    if constexpr (ABL & ABL_NO_BARRIER) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");   \
+    else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");                     \
+    WM_READA(xa0, xa1, 0);                                                                            \
+    WM_BLOAD(bq[2 - 2 * (P)], pub, 0);   /* free since the stage before: out first */                  \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+    if ((KC) > 0) { WM_YMFMA_R(bq[3 - 2 * (P)], acc[XI]); }                                           \
+    else if ((XI) > 0) { WM_YMFMA_R(bq[3 - 2 * (P)], acc[XP]); }                                      \
+    else if (nu > 0) { WM_YMFMA_R(bq[3 - 2 * (P)], acc[5]); WM_FOLD(nup); }                           \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+    /* the next stage's B, behind Y(s-1), which read the registers its groups 2, 3 go to */           \
+    WM_BLOAD(bq[3 - 2 * (P)], pub, 2);                                                                \
+    {                                                                                                 \
+      const int nb = cur >= 1 ? cur - 1 : 2;   /* (cur + 2) % 3: the previous stage's buffer */         \
+      WM_DMA(nb, pvo, puo);                                                                           \
+      pub = puo;                                                                                      \
+      WM_PF_ADVANCE();                                                                                \
+    }                                                                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   /* the X reads (issued 16 MFMAs ago) */        \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+    if ((KC) == 0) { WM_MFMA1_Z(xa0, xa1, bq[2 * (P)], 0, acc[XI]); }   /* a plane's first MFMAs: C = 0 */ \
+    else { WM_MFMA1(xa0, xa1, bq[2 * (P)], 0, acc[XI]); }                                             \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+    WM_READA(ya0, ya1, 2);                                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+    WM_MFMA1(xa0, xa1, bq[2 * (P)], 1, acc[XI]);                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                                \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                \
+    cur = cur == 2 ? 0 : cur + 1;                                                                     \
+  } while (0)
+  static_assert(WM_VM1 == 2, "the stage barrier's vmcnt(2) of BSRC = 1 counts the A DMA instructions a wave issues per stage");
+  /* a plane of an even number of stages: pairs from parity 0 */
+#define WM_PLANE_E(XI, XP) for (int kc = 0; kc < NK; kc += 2) { WM_STAGE1(XI, XP, 0, kc); WM_STAGE1(XI, XP, 1, kc + 1); }
+  /* a plane of an odd number of stages starting at parity P0: one stage, then pairs from the other parity */
+#define WM_PLANE_O(XI, XP, P0)                                                                        \
+  WM_STAGE1(XI, XP, P0, 0);                                                                           \
+  for (int kc = 1; kc < NK; kc += 2) { WM_STAGE1(XI, XP, 1 - (P0), kc); WM_STAGE1(XI, XP, P0, kc + 1); }
+
   // nu - 1 as a scalar loop variable of its own: written `nu - 1` next to the `nu > 0` test the compiler fuses the two into one
   // VECTOR subtract-with-borrow, whose result now outlives the X reads of the stage (one VGPR more than the kernel had)
   int nup = -1;
-  for (int nu = 0; nu < 6; nu++) {
-    for (int kc = 0; kc < NK; kc++) WM_STAGE(0, 5);
-    for (int kc = 0; kc < NK; kc++) WM_STAGE(1, 0);
-    for (int kc = 0; kc < NK; kc++) WM_STAGE(2, 1);
-    for (int kc = 0; kc < NK; kc++) WM_STAGE(3, 2);
-    for (int kc = 0; kc < NK; kc++) WM_STAGE(4, 3);
-    for (int kc = 0; kc < NK; kc++) WM_STAGE(5, 4);
-    nup = nu;
+  if constexpr (BSRC == 0) {
+    for (int nu = 0; nu < 6; nu++) {
+      for (int kc = 0; kc < NK; kc++) WM_STAGE0(0, 5);
+      for (int kc = 0; kc < NK; kc++) WM_STAGE0(1, 0);
+      for (int kc = 0; kc < NK; kc++) WM_STAGE0(2, 1);
+      for (int kc = 0; kc < NK; kc++) WM_STAGE0(3, 2);
+      for (int kc = 0; kc < NK; kc++) WM_STAGE0(4, 3);
+      for (int kc = 0; kc < NK; kc++) WM_STAGE0(5, 4);
+      nup = nu;
+    }
+  } else if constexpr (ODD == 0) {
+    for (int nu = 0; nu < 6; nu++) {
+      WM_PLANE_E(0, 5) WM_PLANE_E(1, 0) WM_PLANE_E(2, 1) WM_PLANE_E(3, 2) WM_PLANE_E(4, 3) WM_PLANE_E(5, 4)
+      nup = nu;
+    }
+  } else {
+    for (int nu = 0; nu < 6; nu++) {
+      WM_PLANE_O(0, 5, 0) WM_PLANE_O(1, 0, 1) WM_PLANE_O(2, 1, 0) WM_PLANE_O(3, 2, 1) WM_PLANE_O(4, 3, 0) WM_PLANE_O(5, 4, 1)
+      nup = nu;
+    }
   }
   // drain: K groups 2, 3 of the last stage, the last column, and every LDS read before the buffers
   // are recycled for the epilogue
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  WM_MFMA(ya0, ya1, yb, acc[5]);
+  if constexpr (BSRC == 0) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    WM_MFMA(ya0, ya1, yb, acc[5]);
+  } else {
+    // The last stage's parked B loads went into bq[0], bq[1], which nothing reads any more: they have landed (vmcnt(2):
+    // only the last stage's two A DMAs may still fly) before the compiler may give those registers to the fold. The
+    // number of stages, 36 NK, is even: the last stage's K groups 2, 3 are in bq[3].
+    asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    WM_MFMA(ya0, ya1, bq[3], acc[5]);
+  }
   WM_FOLD(5);
   // all waves' parked prefetch DMAs have landed before the ring becomes the epilogue's staging buffer: the DMAs are
   // inline asm, so the compiler's __syncthreads() is a bare s_barrier without the vmcnt(0) it would need (see
   // csrc/fc_mfma.hip: the same omission corrupted output rows there)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-#undef WM_STAGE
+#undef WM_STAGE0
+#undef WM_STAGE1
+#undef WM_YMFMA_R
+#undef WM_PLANE_E
+#undef WM_PLANE_O
+#undef WM_BLOAD
+#undef WM_READA
+#undef WM_READA_AT
 #undef WM_READ
 #undef WM_READ_AT
 #undef WM_DSREAD
@@ -573,10 +722,12 @@ extern "C" int pcnn_winograd43_conv_workspace_bytes(int B, int H, int W, int Cin
   return PCNN_OK;
 }
 
-extern "C" int pcnn_winograd43_conv_fwd(const float* v, const float* ut, const float* bias, int B, int H,
-                                        int W, int Cin, int Cout, int groups, int relu, int pool,
-                                        float* y, float* y_pool, void* workspace, size_t workspace_bytes,
-                                        void* stream_)
+// Both entries of the kernel: `packed` = the filter bank is the fragment-major one of pcnn_winograd43_pack_filters_fwd
+// and the kernel takes it straight into registers (BSRC = 1).
+static int wino43_conv_launch(bool packed, const float* v, const float* ut, const float* bias, int B, int H,
+                              int W, int Cin, int Cout, int groups, int relu, int pool,
+                              float* y, float* y_pool, void* workspace, size_t workspace_bytes,
+                              void* stream_)
 {
   PCNN_REQUIRE(B >= 1 && H >= 1 && W >= 1, PCNN_EINVAL, "winograd43_conv: bad shape %dx%dx%d", B, H, W);
   PCNN_REQUIRE(Cin >= 64 && Cin % 64 == 0, PCNN_EINVAL, "winograd43_conv: input channels must be a multiple of 64 (got %d)", Cin);
@@ -598,7 +749,8 @@ extern "C" int pcnn_winograd43_conv_fwd(const float* v, const float* ut, const f
   const long long nbt = (long long)groups * ((tpg + WM_BT - 1) / WM_BT);
   const long long blocks = ((nbt + 7) / 8) * 8 * ncb;
   PCNN_REQUIRE(blocks < (1ll << 31), PCNN_EINVAL, "winograd43_conv: grid too large");
-  // the kernel addresses a plane of V and of U^T with 32-bit byte offsets from 64-bit plane bases
+  // the kernel addresses a plane of V and of U^T with 32-bit byte offsets from 64-bit plane bases (the packed bank's plane
+  // is as large as the row-major one's, Cout * Cin floats; there the lane's offset is 16 * lane and the rest rides in the base)
   PCNN_REQUIRE(T * Cin < (1ll << 30) && (long long)Cout * Cin < (1ll << 30), PCNN_EINVAL,
                "winograd43_conv: a transform plane of %lld x %d (or %d x %d) floats exceeds the kernel's 32-bit byte offsets", T, Cin, Cout, Cin);
   // optional Cin split for launches that cannot fill the chip (needs the caller's workspace)
@@ -616,8 +768,14 @@ extern "C" int pcnn_winograd43_conv_fwd(const float* v, const float* ut, const f
   int mode = (ncb == 8 && u_bytes > v_bytes) ? 1 : 0;
   if (env_mode >= 0) mode = ((env_mode & 1) && ncb == 8) ? 1 : 0;
   const long long nblocks = (mode & 1) ? 8 * nbt : blocks;
-#define WM_GO(P, Y, BIAS, RELU, KS, STRIDE) PCNN_LAUNCH((wino43_mfma_kernel<P>), dim3((unsigned)nblocks, KS), dim3(64 * WM_NW), 0, stream, v, ut, BIAS, Y, y_pool, \
+#define WM_GO_(K, Y, BIAS, RELU, KS, STRIDE) PCNN_LAUNCH(K, dim3((unsigned)nblocks, KS), dim3(64 * WM_NW), 0, stream, v, ut, BIAS, Y, y_pool, \
                              H, W, Cin, Cout, Ht, Wt, T, tpg, RELU, (int)nbt, ncb, KS, (long long)(STRIDE), mode)
+#define WM_GO(P, Y, BIAS, RELU, KS, STRIDE)                                      \
+  do {                                                                           \
+    if (packed && ((Cin / WM_KC / (KS)) & 1)) WM_GO_((wino43_mfma_kernel<P, 1, 0, 1>), Y, BIAS, RELU, KS, STRIDE); \
+    else if (packed) WM_GO_((wino43_mfma_kernel<P, 1>), Y, BIAS, RELU, KS, STRIDE);   \
+    else WM_GO_((wino43_mfma_kernel<P>), Y, BIAS, RELU, KS, STRIDE);             \
+  } while (0)
   if (S == 1) {
     if (pool == 0) WM_GO(0, y, bias, relu, 1, 0); else if (pool == 1) WM_GO(1, y, bias, relu, 1, 0); else WM_GO(2, y, bias, relu, 1, 0);
   } else {
@@ -632,5 +790,60 @@ extern "C" int pcnn_winograd43_conv_fwd(const float* v, const float* ut, const f
     else
       PCNN_LAUNCH(wino43_splitk_reduce_kernel<2>, dim3(rgrid), dim3(256), 0, stream, part, S, (long long)out_elems, bias, relu, y, y_pool, B, H, W, Cout, B / groups);
   }
-  return check_launch("winograd43_conv_fwd");
+  return check_launch(packed ? "winograd43_conv_packed_fwd" : "winograd43_conv_fwd");
+}
+
+extern "C" int pcnn_winograd43_conv_fwd(const float* v, const float* ut, const float* bias, int B, int H,
+                                        int W, int Cin, int Cout, int groups, int relu, int pool,
+                                        float* y, float* y_pool, void* workspace, size_t workspace_bytes,
+                                        void* stream_)
+{
+  return wino43_conv_launch(false, v, ut, bias, B, H, W, Cin, Cout, groups, relu, pool, y, y_pool, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int pcnn_winograd43_conv_packed_fwd(const float* v, const float* utp, const float* bias, int B, int H,
+                                               int W, int Cin, int Cout, int groups, int relu, int pool,
+                                               float* y, float* y_pool, void* workspace, size_t workspace_bytes,
+                                               void* stream_)
+{
+  return wino43_conv_launch(true, v, utp, bias, B, H, W, Cin, Cout, groups, relu, pool, y, y_pool, workspace, workspace_bytes, stream_);
+}
+
+namespace {
+
+// ut [group][36][Cout][Cin] -> utp [group][36][Cout/16][Cin/64][4 (K group j)][64 (lane = 16 lk + lr)][4]:
+//   utp[g][k][n16][kc][j][16 lk + lr][e] = ut[g][k][16 n16 + lr][64 kc + 16 j + 4 lk + e]
+// — the order in which a wave of wino43_mfma_kernel<., 1> consumes its B operand: one wave-wide 16-byte load is one
+// contiguous KB, a stage's four loads 4 KB. A plain permutation, one float4 per thread, run once per filter.
+__global__ __launch_bounds__(256) void wino43_pack_filters_kernel(const float* __restrict__ ut, float* __restrict__ utp,
+                                                                  int Cin, int Cout, long long total4)
+{
+  const int nkc = Cin / WM_KC, n16n = Cout / 16;
+  for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total4; o += (long long)gridDim.x * 256) {
+    const int l = (int)(o & 63), j = (int)((o >> 6) & 3);
+    long long r = o >> 8;
+    const int kc = (int)(r % nkc); r /= nkc;
+    const int n16 = (int)(r % n16n);
+    const long long gk = r / n16n;   // 36 g + k
+    const int lr = l & 15, lk = l >> 4;
+    const long long src = (gk * Cout + 16 * n16 + lr) * Cin + 64 * kc + 16 * j + 4 * lk;
+    *reinterpret_cast<v4f*>(utp + 4 * o) = *reinterpret_cast<const v4f*>(ut + src);
+  }
+}
+
+}  // namespace
+
+extern "C" int pcnn_winograd43_pack_filters_fwd(const float* ut, int Cin, int Cout, int groups, float* utp, void* stream_)
+{
+  PCNN_REQUIRE(Cin >= 64 && Cin % 64 == 0, PCNN_EINVAL, "winograd43_pack_filters: input channels must be a multiple of 64 (got %d)", Cin);
+  PCNN_REQUIRE(Cout >= 64 && Cout % 64 == 0, PCNN_EINVAL, "winograd43_pack_filters: output channels must be a multiple of 64 (got %d)", Cout);
+  PCNN_REQUIRE(groups >= 1, PCNN_EINVAL, "winograd43_pack_filters: groups must be positive (got %d)", groups);
+  PCNN_REQUIRE(ut && utp, PCNN_ENULL, "winograd43_pack_filters: NULL pointer");
+  PCNN_REQUIRE(ut != utp, PCNN_EINVAL, "winograd43_pack_filters: not an in-place permutation");
+  PCNN_REQUIRE(aligned16(ut) && aligned16(utp), PCNN_EINVAL, "winograd43_pack_filters: pointers (ut, utp) must be 16-byte aligned");
+  hipStream_t stream = (hipStream_t)stream_;
+  const long long total4 = (long long)groups * 36 * Cout * Cin / 4;
+  const unsigned grid = (unsigned)((total4 + 255) / 256 < 65536 ? (total4 + 255) / 256 : 65536);
+  PCNN_LAUNCH(wino43_pack_filters_kernel, dim3(grid), dim3(256), 0, stream, ut, utp, Cin, Cout, total4);
+  return check_launch("winograd43_pack_filters_fwd");
 }

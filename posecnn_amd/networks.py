@@ -136,8 +136,8 @@ class _RawConv(object):
         # wino  = (M [n*n,T,C], B, H, W): in the Winograd domain, waiting for its output transform
         # first = (x [B,H,W,3], w [3,3,3,C]): a 3-channel first conv not evaluated yet — a following
         #         Winograd conv computes it fused with its own input transform
-        # gemm  = (V [36,T,Cin], Ut [36,Cout,Cin], B, H, W): F(4x4,3x3) input transform done, the fused
-        #         GEMM + output transform kernel still to run (with or without the max-pool)
+        # gemm  = (V [36,T,Cin], Ut [36,Cout,Cin], B, H, W, packed): F(4x4,3x3) input transform done, the fused
+        #         GEMM + output transform kernel still to run (with or without the max-pool); packed: Ut is the fragment-major bank
         # lazy12 = (pending conv1_1 (_RawConv with `first`), name, w): conv1_2 on top of a pending conv1_1, nothing launched
         #         yet — a following 2x2 max_pool runs conv1_1 -> conv1_2 -> pool1 as ONE kernel; anything else that asks for the
         #         tensor gets the unfused pair
@@ -177,6 +177,12 @@ class Network(object):
     def use_fused_train_epilogue(self, on=True):
         self.fused_train_epilogue = bool(on)
         return self
+
+    # The MFMA trunk kernel (`winograd_mfma`) on the fragment-major filter bank (ops.winograd43_pack_filters), which it takes
+    # straight into registers instead of through its LDS ring. Not a route of its own — same kernel, same products, same
+    # bits — but a switch for A/B timing and the equality test (tests/test_gpu_wino_packed.py): set False on an instance for the
+    # row-major bank through LDS.
+    winograd_packed = True
 
     def __init__(self, device="cuda", seed=3, init="he", trainable=True):
         self.inputs = []
@@ -244,13 +250,13 @@ class Network(object):
             elif raw.first is not None:
                 raw.out = ops.conv3x3_c3(raw_frame_blob(raw.first[0]), raw.first[1], raw.bias, raw.relu)
             elif raw.gemm is not None:
-                v, ut, B, H, W = raw.gemm
-                raw.out = ops.winograd43_conv(v, ut, raw.bias, B, H, W, raw.relu, pool=0)
+                v, ut, B, H, W, pk = raw.gemm
+                raw.out = ops.winograd43_conv(v, ut, raw.bias, B, H, W, raw.relu, pool=0, packed=pk)
             elif raw.lazy12 is not None:   # somebody wants conv1_2 un-pooled: the unfused pair
                 pf, name12, w2 = raw.lazy12
                 B, H, W = pf.shape[:3]
-                raw.out = ops.winograd43_conv(self._first_conv_v(pf), self._winograd_filter(name12, w2, transposed=True), raw.bias,
-                                              B, H, W, raw.relu, pool=0)
+                ut, pk = self._winograd_bank(name12, w2)
+                raw.out = ops.winograd43_conv(self._first_conv_v(pf), ut, raw.bias, B, H, W, raw.relu, pool=0, packed=pk)
             else:
                 raw.out = self._bias_act(raw.y, raw.bias, raw.relu)
         return raw.out
@@ -275,6 +281,15 @@ class Network(object):
             u = ops.winograd_filter(w, self.winograd_tile)
             return u.transpose(1, 2).contiguous() if transposed else u
         return self._derived(("wino", name, transposed), (w,), build, self.winograd_tile)
+
+    def _winograd_bank(self, name, w):
+        """(filter bank, packed) for ops.winograd43_conv: U^T as `_winograd_filter` keeps it, or with `winograd_packed` its
+        fragment-major permutation, kept next to it and rebuilt with it — once per version of the variable."""
+        if not self.winograd_packed:
+            return self._winograd_filter(name, w, transposed=True), False
+        return self._derived(("wino_packed", name), (w,),
+                             lambda: ops.winograd43_pack_filters(self._winograd_filter(name, w, transposed=True)),
+                             self.winograd_tile), True
 
     def _derived(self, slot, sources, build, extra=None):
         """The value `build()` makes out of the variables `sources`, kept under `slot` until one of them changes — the ONE
@@ -303,18 +318,18 @@ class Network(object):
         + output transform, optionally the following 2x2 max-pool) for Cin, Cout multiples of 64;
         framework batched GEMM + output transform kernel otherwise."""
         if self.winograd_mfma and c_i % 64 == 0 and c_o % 64 == 0:
-            ut = self._winograd_filter(name, w, transposed=True)
+            ut, pk = self._winograd_bank(name, w)
             if timing is not None:
                 timing[1].record()   # the MFMA kernel is timed by the library's own events
                 self.conv_timing.append((name, timing[2], timing[2], timing[0], timing[1]))
             even = H_ % 2 == 0 and W_ % 2 == 0
             if name in self.defer_act and even:
-                return _RawConv(None, b, relu, gemm=(v, ut, B_, H_, W_))      # the following max_pool decides
+                return _RawConv(None, b, relu, gemm=(v, ut, B_, H_, W_, pk))      # the following max_pool decides
             if name in self.dual_pool and even:
                 out = _RawConv(None, b, relu)
-                out.out, out.pooled = ops.winograd43_conv(v, ut, b, B_, H_, W_, relu, pool=2)
+                out.out, out.pooled = ops.winograd43_conv(v, ut, b, B_, H_, W_, relu, pool=2, packed=pk)
                 return out
-            return ops.winograd43_conv(v, ut, b, B_, H_, W_, relu, pool=0)
+            return ops.winograd43_conv(v, ut, b, B_, H_, W_, relu, pool=0, packed=pk)
         m = torch.bmm(v, self._winograd_filter(name, w))
         executed = 2.0 * m.numel() * c_i
         if timing is not None:
@@ -552,8 +567,8 @@ class Network(object):
                 if input.first is not None:
                     return F.max_pool2d(_nchw(self._activate(input)), 2, 2).permute(0, 2, 3, 1).contiguous()
                 if input.gemm is not None:
-                    v, ut, B_, H_, W_ = input.gemm
-                    return ops.winograd43_conv(v, ut, input.bias, B_, H_, W_, input.relu, pool=1)
+                    v, ut, B_, H_, W_, pk = input.gemm
+                    return ops.winograd43_conv(v, ut, input.bias, B_, H_, W_, input.relu, pool=1, packed=pk)
                 if input.lazy12 is not None:
                     pf, name12, w2 = input.lazy12
                     # the filter bank in the order the kernel's lanes consume it
@@ -1047,7 +1062,9 @@ class vgg16_convs(Network):
             # both (mode 2) whatever `dual_pool` / `fused_pool` say; the other conv -> pool pairs keep only
             # the pooled tensor (mode 1)
             mode = 0 if pool is None else (2 if name == "conv4_3" else 1)
-            out = ops.winograd43_conv(v, wt, bias, B2, h, w_, True, pool=mode, groups=2)
+            if self.winograd_packed:   # keyed on the two filters it is made of, like the conv1_2 fragments above
+                wt = self._derived(("wino_packed", "grouped", li), (va[li][0], vb[li][0]), lambda: ops.winograd43_pack_filters(wt))
+            out = ops.winograd43_conv(v, wt, bias, B2, h, w_, True, pool=mode, groups=2, packed=self.winograd_packed)
             if mode == 2:
                 full, y = out
             else:

@@ -577,11 +577,27 @@ def winograd43_output_both(m, bias, B, H, W, relu=True):
     return y, yp
 
 
-def winograd43_conv(v, ut, bias, B, H, W, relu=True, pool=0, groups=1):
+def winograd43_pack_filters(ut):
+    """ut [groups,36,Cout,Cin] (or [36,Cout,Cin]) -> the fragment-major filter bank of winograd43_conv(packed=True), same
+    shape and size: viewed as [groups,36,Cout/16,Cin/64,4,64,4], element [g,k,n16,kc,j,16*lk+lr,e] is
+    ut[g,k,16*n16+lr,64*kc+16*j+4*lk+e] — the order in which a wave's lanes consume the operand. Once per filter."""
+    ut = _dev(ut, "ut", torch.float32)
+    if ut.dim() not in (3, 4) or ut.shape[-3] != 36:
+        raise ValueError("ut must be [groups, 36, Cout, Cin] or [36, Cout, Cin]")
+    groups = ut.shape[0] if ut.dim() == 4 else 1
+    Cout, Cin = ut.shape[-2], ut.shape[-1]
+    utp = torch.empty_like(ut)
+    check("pcnn_winograd43_pack_filters_fwd",
+          lib().pcnn_winograd43_pack_filters_fwd(_ptr(ut), Cin, Cout, int(groups), _ptr(utp), _stream(ut)))
+    return utp
+
+
+def winograd43_conv(v, ut, bias, B, H, W, relu=True, pool=0, groups=1, packed=False):
     """The 36 Winograd-domain contractions + output transform of F(4x4,3x3) in one fp32-MFMA kernel:
     v [36,T,Cin], ut [groups,36,Cout,Cin] (= winograd_filter(w, 4).transpose(1, 2) per group), bias
     [groups,Cout] -> y [B,H,W,Cout] (pool=0), its 2x2 max-pool [B,H/2,W/2,Cout] (pool=1) or both (pool=2,
-    returns (y, y_pool)). `groups`: image b uses filter set b // (B // groups)."""
+    returns (y, y_pool)). `groups`: image b uses filter set b // (B // groups). `packed`: ut is the bank of
+    winograd43_pack_filters (same shape), which the kernel takes straight into registers; same bits."""
     v = _dev(v, "v", torch.float32)
     ut = _dev(ut, "ut", torch.float32)
     bias = _aligned16(_dev(bias, "bias", torch.float32))
@@ -599,9 +615,10 @@ def winograd43_conv(v, ut, bias, B, H, W, relu=True, pool=0, groups=1):
     check("pcnn_winograd43_conv_workspace_bytes",
           lib().pcnn_winograd43_conv_workspace_bytes(B, H, W, Cin, Cout, int(groups), ctypes.byref(nbytes)))
     ws = _ws(v.device, "wino43_conv").get(nbytes.value, v.device) if nbytes.value else None   # Cin-split partials (small launches only)
-    check("pcnn_winograd43_conv_fwd",
-          lib().pcnn_winograd43_conv_fwd(_ptr(v), _ptr(ut), _ptr(bias), B, H, W, Cin, Cout, int(groups), 1 if relu else 0,
-                                         pool, _ptr(y), _ptr(yp), _ptr(ws), nbytes.value, _stream(v)))
+    fn = "pcnn_winograd43_conv_packed_fwd" if packed else "pcnn_winograd43_conv_fwd"
+    check(fn,
+          getattr(lib(), fn)(_ptr(v), _ptr(ut), _ptr(bias), B, H, W, Cin, Cout, int(groups), 1 if relu else 0,
+                             pool, _ptr(y), _ptr(yp), _ptr(ws), nbytes.value, _stream(v)))
     return (y, yp) if pool == 2 else y
 
 

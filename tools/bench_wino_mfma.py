@@ -47,6 +47,7 @@ def main():
     G, B = a.groups, a.batch * a.groups
     res = {"frames_per_tower": a.batch, "groups": G, "layers": {}}
     tot_mfma = tot_in = tot_lib = tot_fl = 0.0
+    tot_p, tot_b = [0.0, 0.0], [0.0, 0.0]
     with torch.no_grad():
         for name, ci, co, div, pool in LAYERS:
             if a.layers and name not in a.layers.split(","):
@@ -61,8 +62,16 @@ def main():
             ms_in = timeit(lambda: ops.winograd_input(x, 4))
             ms = timeit(lambda: ops.winograd43_conv(v, ut, b, B, H, W, True, pool, G))
             ms0 = timeit(lambda: ops.winograd43_conv(v, ut, b, B, H, W, True, 0, G)) if pool else ms
+            # the packed-filter route (B operand straight into registers), timed around the old one: packed, old, packed, old
+            utp = ops.winograd43_pack_filters(ut)
+            ms_p = timeit(lambda: ops.winograd43_conv(v, utp, b, B, H, W, True, pool, G, packed=True))
+            ms_b = timeit(lambda: ops.winograd43_conv(v, ut, b, B, H, W, True, pool, G))
+            ms_p2 = timeit(lambda: ops.winograd43_conv(v, utp, b, B, H, W, True, pool, G, packed=True))
+            ms_b2 = timeit(lambda: ops.winograd43_conv(v, ut, b, B, H, W, True, pool, G))
             e = {"tiles": v.shape[1], "cin": ci, "cout": co, "pool": pool, "input_transform_ms": round(ms_in, 4),
-                 "mfma_ms": round(ms, 4), "mfma_TFLOPs": round(fl / ms / 1e9, 1), "mfma_nopool_ms": round(ms0, 4)}
+                 "mfma_ms": round(ms, 4), "mfma_TFLOPs": round(fl / ms / 1e9, 1), "mfma_nopool_ms": round(ms0, 4),
+                 "packed_ms": [round(ms_p, 4), round(ms_p2, 4)], "unpacked_ms": [round(ms_b, 4), round(ms_b2, 4)],
+                 "packed_TFLOPs": round(fl / min(ms_p, ms_p2) / 1e9, 1)}
             if not a.no_library:
                 u0 = ops.winograd_filter(w[0], 4)
                 ms_mm = timeit(lambda: torch.bmm(v, u0))
@@ -74,9 +83,11 @@ def main():
                 tot_lib += ms_mm + ms_out
             res["layers"][name] = e
             tot_mfma += ms; tot_in += ms_in; tot_fl += fl
-            del x, v, ut
+            tot_p[0] += ms_p; tot_p[1] += ms_p2; tot_b[0] += ms_b; tot_b[1] += ms_b2
+            del x, v, ut, utp
     res["total"] = {"mfma_ms": round(tot_mfma, 3), "input_transform_ms": round(tot_in, 3), "mfma_TFLOPs": round(tot_fl / tot_mfma / 1e9, 1),
-                    "round1_gemm_plus_output_ms": round(tot_lib, 3)}
+                    "round1_gemm_plus_output_ms": round(tot_lib, 3),
+                    "packed_ms": [round(t, 3) for t in tot_p], "unpacked_ms": [round(t, 3) for t in tot_b]}
     print(json.dumps(res))
 
 

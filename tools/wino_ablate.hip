@@ -11,7 +11,8 @@
 
 #include "../posecnn_amd/csrc/wino_mfma.hip"
 
-template <int ABL>
+// BSRC = 1: `ut` is read as the fragment-major bank (timing only: synthetic data either way); ODD = the parity of Cin / 64
+template <int ABL, int BSRC = 0, int ODD = 0>
 static float run(const float* v, const float* ut, const float* bias, float* y, int H, int W, int Cin, int Cout, long long T, int iters)
 {
   const int Ht = (H + 3) / 4, Wt = (W + 3) / 4;
@@ -21,10 +22,10 @@ static float run(const float* v, const float* ut, const float* bias, float* y, i
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   for (int i = 0; i < 2; i++)
-    hipLaunchKernelGGL((wino43_mfma_kernel<0, ABL>), dim3((unsigned)blocks), dim3(64 * WM_NW), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
+    hipLaunchKernelGGL((wino43_mfma_kernel<0, BSRC, ABL, ODD>), dim3((unsigned)blocks), dim3(64 * WM_NW), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
   hipEventRecord(e0, 0);
   for (int i = 0; i < iters; i++)
-    hipLaunchKernelGGL((wino43_mfma_kernel<0, ABL>), dim3((unsigned)blocks), dim3(64 * WM_NW), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
+    hipLaunchKernelGGL((wino43_mfma_kernel<0, BSRC, ABL, ODD>), dim3((unsigned)blocks), dim3(64 * WM_NW), 0, 0, v, ut, bias, y, (float*)nullptr, H, W, Cin, Cout, Ht, Wt, T, T, 1, (int)nbt, ncb, 1, 0, 0);
   hipEventRecord(e1, 0);
   hipEventSynchronize(e1);
   float ms = 0;
@@ -72,6 +73,16 @@ int main(int argc, char** argv)
   R(ABL_NO_STORES, "epilogue without its global stores");
   R(ABL_EPI_REGS_ONLY, "epilogue = bias + ReLU only (no staging, no stores)");
   R(0, "full kernel (again 2)");
+  // the packed-filter route (B operand from global memory into registers); Cin / 64 even and odd take different instances
+#define RB(ABL, WHAT) { float ms = (Cin / 64) & 1 ? run<ABL, 1, 1>(v, ut, bias, y, H, W, Cin, Cout, T, it) : run<ABL, 1, 0>(v, ut, bias, y, H, W, Cin, Cout, T, it); \
+                        printf("%-44s %8.3f ms  %6.1f TFLOP/s-equivalent\n", WHAT, ms, fl / ms / 1e9); }
+  RB(0, "packed: full kernel");
+  RB(ABL_NO_EPILOGUE, "packed: no epilogue");
+  RB(ABL_NO_EPILOGUE | ABL_NO_B_LOADS, "packed: no epilogue, no B loads");
+  RB(ABL_NO_EPILOGUE | ABL_NO_DMA, "packed: no epilogue, no A DMA");
+  RB(ABL_NO_EPILOGUE | ABL_NO_LDS_READS, "packed: no epilogue, no LDS reads");
+  RB(ABL_NO_EPILOGUE | ABL_NO_BARRIER, "packed: no epilogue, no barrier");
+  RB(0, "packed: full kernel (again)");
   R(0, "full kernel (last)");
   return 0;
 }
