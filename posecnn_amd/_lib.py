@@ -1,6 +1,6 @@
 """ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h, include/posecnn_hip_train.h,
 include/posecnn_hip_frontend.h, include/posecnn_hip_synth.h, include/posecnn_hip_augment.h, include/posecnn_hip_loss.h,
-include/posecnn_hip_vertex_loss.h, include/posecnn_hip_trunk_train.h, include/posecnn_hip_pose3d.h and
+include/posecnn_hip_vertex_loss.h, include/posecnn_hip_trunk_train.h, include/posecnn_hip_pose3d.h, include/posecnn_hip_pose2d.h and
 include/posecnn_hip_wino_packed.h).
 
 This is the Python-side analogue of the reference's ``tf.load_op_library('<op>.so')`` stubs
@@ -186,6 +186,19 @@ POSE3D_SIGNATURES = {
                                          _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# the colour-only pose entries of include/posecnn_hip_pose2d.h (same library, same ABI version)
+POSE2D_SIGNATURES = {
+    "pcnn_pose2d_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "pcnn_pose2d_prepare_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "pcnn_pose2d_sample_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_float, c_float, c_float, _P, _P, _P, _P, _P]),
+    "pcnn_pose2d_round_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                      _P, _P, _P, _P]),
+    "pcnn_pose2d_estimate_fwd": (c_int, [_P, _P, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int,
+                                         _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 # the packed-filter route of the Winograd trunk kernel, include/posecnn_hip_wino_packed.h (same library, same ABI version)
 WINO_PACKED_SIGNATURES = {
     "pcnn_winograd43_pack_filters_fwd": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
@@ -240,7 +253,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) +\
                 list(SYNTH_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) +\
                 list(VERTEX_LOSS_SIGNATURES.items()) + list(TRUNK_TRAIN_SIGNATURES.items()) + list(POSE3D_SIGNATURES.items()) +\
-                list(WINO_PACKED_SIGNATURES.items()):
+                list(POSE2D_SIGNATURES.items()) + list(WINO_PACKED_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args

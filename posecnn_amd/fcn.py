@@ -204,19 +204,9 @@ def _get_bb2D(extent, pose, intrinsic_matrix):
     return np.array([np.min(x2d[0, :]), np.min(x2d[1, :]), np.max(x2d[0, :]), np.max(x2d[1, :])], dtype=np.float32)
 
 
-def poses_from_vertmap_3d(labels, im_depth, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None):
-    """The depth leg of lib/fcn/test.py:1353-1401 after the network: `Synthesizer.estimate_poses_3d` on the label map,
-    the depth frame and the object-coordinate field, then one row per class with poses_tmp[2, 3, j] > 0:
-    rois [n,6] = (0, class, x1, y1, x2, y2 of `_get_bb2D`), poses [n,7] = (mat2quat(R), t). The rows feed
-    `Synthesizer.icp_python(..., channel_roi=6, ...)` (:1416)."""
-    from .icp import Synthesizer, mat2quat
-    K = np.asarray(meta_data["intrinsic_matrix"], dtype=np.float64)
-    factor = float(np.asarray(meta_data["factor_depth"]).reshape(-1)[0])
-    syn = synthesizer if synthesizer is not None else Synthesizer(meshes=[], device=device)
-    extents = np.asarray(extents, dtype=np.float32)
-    poses_tmp = np.zeros((3, 4, num_classes), dtype=np.float32)
-    syn.estimate_poses_3d(labels, im_depth, vertex_pred, extents, poses_tmp, num_classes, K[0, 0], K[1, 1], K[0, 2], K[1, 2],
-                          factor, seed=seed)
+def _pose_rows(poses_tmp, extents, K, num_classes):
+    """lib/fcn/test.py:1365-1378 and :1386-1399: one row per class with poses_tmp[2, 3, j] > 0"""
+    from .icp import mat2quat
     found = [j for j in range(num_classes) if poses_tmp[2, 3, j] > 0]
     rois = np.zeros((len(found), 6), dtype=np.float32)
     poses = np.zeros((len(found), 7), dtype=np.float32)
@@ -228,14 +218,47 @@ def poses_from_vertmap_3d(labels, im_depth, vertex_pred, meta_data, extents, num
     return rois, poses
 
 
-def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classes, seed=0, device="cuda"):
+def poses_from_vertmap_3d(labels, im_depth, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None):
+    """The depth leg of lib/fcn/test.py:1353-1401 after the network: `Synthesizer.estimate_poses_3d` on the label map,
+    the depth frame and the object-coordinate field, then one row per class with poses_tmp[2, 3, j] > 0:
+    rois [n,6] = (0, class, x1, y1, x2, y2 of `_get_bb2D`), poses [n,7] = (mat2quat(R), t). The rows feed
+    `Synthesizer.icp_python(..., channel_roi=6, ...)` (:1416)."""
+    from .icp import Synthesizer
+    K = np.asarray(meta_data["intrinsic_matrix"], dtype=np.float64)
+    factor = float(np.asarray(meta_data["factor_depth"]).reshape(-1)[0])
+    syn = synthesizer if synthesizer is not None else Synthesizer(meshes=[], device=device)
+    extents = np.asarray(extents, dtype=np.float32)
+    poses_tmp = np.zeros((3, 4, num_classes), dtype=np.float32)
+    syn.estimate_poses_3d(labels, im_depth, vertex_pred, extents, poses_tmp, num_classes, K[0, 0], K[1, 1], K[0, 2], K[1, 2],
+                          factor, seed=seed)
+    return _pose_rows(poses_tmp, extents, K, num_classes)
+
+
+def poses_from_vertmap_2d(labels, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None):
+    """The colour leg of lib/fcn/test.py:1362-1378 after the network: `Synthesizer.estimate_poses_2d` on the label map and
+    the object-coordinate field alone, then the rows of `poses_from_vertmap_3d`: rois_rgb [n,6], poses_rgb [n,7]."""
+    from .icp import Synthesizer
+    K = np.asarray(meta_data["intrinsic_matrix"], dtype=np.float64)
+    syn = synthesizer if synthesizer is not None else Synthesizer(meshes=[], device=device)
+    extents = np.asarray(extents, dtype=np.float32)
+    poses_tmp = np.zeros((3, 4, num_classes), dtype=np.float32)
+    syn.estimate_poses_2d(labels, vertex_pred, extents, poses_tmp, num_classes, K[0, 0], K[1, 1], K[0, 2], K[1, 2], seed=seed)
+    return _pose_rows(poses_tmp, extents, K, num_classes)
+
+
+def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classes, seed=0, device="cuda", rgb_poses=False):
     """lib/fcn/test.py:1353-1401 for a `vertex_reg_3d` network (lov_color_3d.yml, linemod_*_3d.yml): the graph gives
     label_2d and the per-pixel object coordinates, `poses_from_vertmap_3d` turns them and the depth frame into poses.
     `im` BGR uint8 and `im_depth` uint16 [H,W], padded to a multiple of 16 by the caller; meta_data needs
     intrinsic_matrix and factor_depth. Returns (labels_2d [H,W] int32, probs [H,W,C], vertex_pred [H,W,3C], rois [n,6],
-    poses [n,7])."""
+    poses [n,7]).
+    rgb_poses=True: the colour leg (:1362-1378) instead — the last two are `poses_from_vertmap_2d`'s rois_rgb and
+    poses_rgb, no depth frame enters the poses, and `im_depth` may be None for the 'COLOR' input format (meta_data then
+    needs intrinsic_matrix only)."""
     if not getattr(net, "vertex_reg_3d", False):
         raise ValueError("im_segment_single_frame_3d needs a network built with vertex_reg_3d=True")
+    if im_depth is None and not (rgb_poses and net.input_format == "COLOR"):
+        raise ValueError("im_depth may be None only with rgb_poses=True and the COLOR input format")
     if net.input_format in ("DEPTH", "NORMAL"):
         blob, data_p = _depth_frame_input(net.input_format, im_depth, meta_data, torch.device(device)), None
     else:
@@ -247,7 +270,10 @@ def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classe
     net.run(feed)
     g = lambda n: net.get_output(n).detach().cpu().numpy()
     labels_2d, probs, vertex_pred = g("label_2d")[0].astype(np.int32), g("prob_normalized")[0], g("vertex_pred")[0]
-    rois, poses = poses_from_vertmap_3d(labels_2d, im_depth, vertex_pred, meta_data, extents, num_classes, seed, device)
+    if rgb_poses:
+        rois, poses = poses_from_vertmap_2d(labels_2d, vertex_pred, meta_data, extents, num_classes, seed, device)
+    else:
+        rois, poses = poses_from_vertmap_3d(labels_2d, im_depth, vertex_pred, meta_data, extents, num_classes, seed, device)
     return labels_2d, probs, vertex_pred, rois, poses
 
 

@@ -397,6 +397,22 @@ class Synthesizer:
             if found[j]:
                 poses[:, :, j] = out[j]
 
+    def estimate_poses_2d(self, labels, vertmap, extents, poses, num_classes, fx, fy, px, py, seed=0):
+        """`Synthesizer.estimate_poses_2d` (synthesizer.pyx:75-84 -> estimatePose2D, synthesize.cpp:1571-1767) with the
+        reference's arguments — `estimate_poses_3d`'s without the depth frame and its factor; poses f32 [3,4,num_classes]
+        is filled in place in the same way. One frame through ops.estimate_poses_2d; `seed` keys its sampler."""
+        from . import ops
+        dev = self.device
+        labels_t = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)[None]).to(dev)
+        vert_t = torch.from_numpy(np.ascontiguousarray(vertmap, dtype=np.float32)[None]).to(dev)
+        ext_t = torch.from_numpy(np.ascontiguousarray(extents, dtype=np.float32).reshape(int(num_classes), 3)).to(dev)
+        intr = torch.tensor([[fx, fy, px, py]], dtype=torch.float32, device=dev)
+        out, _, _, _, num_hyps = ops.estimate_poses_2d(labels_t, vert_t, ext_t, intr, seed=seed)
+        out, found = out[0].cpu().numpy(), num_hyps[0].cpu().numpy() > 0
+        for j in range(int(num_classes)):
+            if found[j]:
+                poses[:, :, j] = out[j]
+
     def icp_python(self, labelmap, depth, parameters, height, width, num_roi, channel_roi, rois, poses, outputs, outputs_icp,
                    maxError, iterations=8, min_pixels=400, radius=0.01):
         """`Synthesizer::icp_python` -> `solveICP`. parameters = (fx, fy, px, py, znear, zfar, factor_depth);

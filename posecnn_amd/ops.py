@@ -27,6 +27,7 @@ __all__ = [
     "label_head_loss", "label_head_loss_grad", "vertex_head_loss", "vertex_head_loss_grad",
     "bias_relu_train_", "bias_relu_train_grad", "bias_relu_pool2_train", "bias_relu_pool2_train_grad",
     "estimate_poses_3d", "pose3d_prepare", "pose3d_sample", "pose3d_round",
+    "estimate_poses_2d", "pose2d_prepare", "pose2d_sample", "pose2d_round",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1806,4 +1807,128 @@ def estimate_poses_3d(label_2d, depth, vertex_pred, extents, intrinsics, factor_
                                          int(max_pixels), int(ref_it), int(min_area), float(inlier_threshold), float(min_dist),
                                          int(max_attempts), _ptr(poses64), _ptr(poses), _ptr(inliers), _ptr(ref_steps),
                                          _ptr(num_hyps), _ptr(ws), nbytes.value, _stream(poses)))
+    return poses, poses64, inliers, ref_steps, num_hyps
+
+
+# ------------------------------------------------------------------------------------------------
+# 3-D vertex route without depth: preemptive RANSAC with P3P hypotheses and a Gauss-Newton refit (include/posecnn_hip_pose2d.h)
+POSE2D_DEFAULTS = dict(hypotheses=256, pixel_batch=1000, max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=10.0,
+                       min_dist2d=10.0, min_dist3d=0.01, min_pixels=10, max_attempts=1024)   # synthesize.cpp:1590-1599; max_attempts is ours
+
+
+def _pose2d_frames(label_2d, vertex_pred, extents, intrinsics=None):
+    label_2d = _dev(label_2d, "label_2d", torch.int32)
+    vertex_pred = _dev(vertex_pred, "vertex_pred", torch.float32)
+    extents = _dev(extents, "extents", torch.float32)
+    if label_2d.dim() != 3:
+        raise ValueError("label_2d must be [B,H,W] (got %s)" % (tuple(label_2d.shape),))
+    B, H, W = label_2d.shape
+    if extents.dim() != 2 or extents.shape[1] != 3:
+        raise ValueError("extents must be [C,3] (got %s)" % (tuple(extents.shape),))
+    C = extents.shape[0]
+    if tuple(vertex_pred.shape) != (B, H, W, 3 * C):
+        raise ValueError("vertex_pred must be [%d,%d,%d,%d] (got %s)" % (B, H, W, 3 * C, tuple(vertex_pred.shape)))
+    if intrinsics is not None:
+        intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+        if tuple(intrinsics.shape) != (B, 4):
+            raise ValueError("intrinsics must be [B,4] rows (fx, fy, px, py) with B = %d (got %s)" % (B, tuple(intrinsics.shape)))
+    return label_2d, vertex_pred, extents, intrinsics, B, H, W, C
+
+
+def pose2d_prepare(label_2d, vertex_pred, extents):
+    """The correspondence records of `estimate_poses_2d`: -> (records f32 [B,H*W,6] rows (pixel x, pixel y, 0, obj xyz),
+    compacted per (frame, class) in raster order, counts int32 [B,C], offsets int32 [B,C]). Rows past a frame's total are
+    not written."""
+    label_2d, vertex_pred, extents, _, B, H, W, C = _pose2d_frames(label_2d, vertex_pred, extents)
+    dev = label_2d.device
+    records = torch.empty((B, H * W, 6), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, C), dtype=torch.int32, device=dev)
+    offsets = torch.empty((B, C), dtype=torch.int32, device=dev)
+    check("pcnn_pose2d_prepare_fwd",
+          lib().pcnn_pose2d_prepare_fwd(_ptr(label_2d), _ptr(vertex_pred), _ptr(extents), B, H, W, C, _ptr(records), _ptr(counts),
+                                        _ptr(offsets), _stream(records)))
+    return records, counts, offsets
+
+
+def pose2d_sample(records, counts, offsets, extents, intrinsics, height, width, seed=0, streams=None, hypotheses=256,
+                  max_attempts=1024, min_area=400, inlier_threshold=10.0, min_dist2d=10.0, min_dist3d=0.01):
+    """One 4-point hypothesis per (frame, h) from `pose2d_prepare`'s records — P3P on three pairs, the fourth chooses the
+    root: -> (hyp_pose f64 [B,hypotheses,3,4], hyp_class int32 [B,hypotheses] (0: none found), hyp_attempt int32 (the
+    accepted attempt, -1), hyp_rec int32 [..,4] (the four records, indices inside their class))."""
+    H, W = int(height), int(width)
+    records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
+    extents = _dev(extents, "extents", torch.float32)
+    intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+    if tuple(extents.shape) != (C, 3) or tuple(intrinsics.shape) != (B, 4):
+        raise ValueError("extents must be [%d,3] and intrinsics [%d,4]" % (C, B))
+    dev = records.device
+    streams = _pose3d_streams(streams, B, dev)
+    s0, s1 = _pose3d_seed(seed)
+    n = int(hypotheses)
+    hyp_pose = torch.empty((B, max(n, 0), 3, 4), dtype=torch.float64, device=dev)
+    hyp_class = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
+    hyp_attempt = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
+    hyp_rec = torch.empty((B, max(n, 0), 4), dtype=torch.int32, device=dev)
+    check("pcnn_pose2d_sample_fwd",
+          lib().pcnn_pose2d_sample_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(extents), _ptr(intrinsics), _ptr(streams),
+                                       s0, s1, B, H, W, C, n, int(max_attempts), int(min_area), float(inlier_threshold),
+                                       float(min_dist2d), float(min_dist3d), _ptr(hyp_pose), _ptr(hyp_class), _ptr(hyp_attempt),
+                                       _ptr(hyp_rec), _stream(records)))
+    return hyp_pose, hyp_class, hyp_attempt, hyp_rec
+
+
+def pose2d_round(records, counts, offsets, intrinsics, hyp_pose, hyp_class, height, width, round, pixel_batch=1000,
+                 max_pixels=1000, inlier_threshold=10.0):
+    """ONE count -> rank -> halve -> Gauss-Newton refit round of the preemptive loop on the given hypotheses (hyp_class 0:
+    empty slot): -> (pose_out f64 [B,n,3,4], class_out int32 [B,n] (0 where the slot was dropped), inliers_out int32 [B,n])."""
+    H, W = int(height), int(width)
+    records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
+    intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+    hyp_pose = _dev(hyp_pose, "hyp_pose", torch.float64)
+    hyp_class = _dev(hyp_class, "hyp_class", torch.int32)
+    if tuple(intrinsics.shape) != (B, 4):
+        raise ValueError("intrinsics must be [%d,4] (got %s)" % (B, tuple(intrinsics.shape)))
+    if hyp_class.dim() != 2 or hyp_class.shape[0] != B or tuple(hyp_pose.shape) != tuple(hyp_class.shape) + (3, 4):
+        raise ValueError("hyp_class must be [B,n] and hyp_pose [B,n,3,4] (got %s, %s)" % (tuple(hyp_class.shape), tuple(hyp_pose.shape)))
+    n = hyp_class.shape[1]
+    dev = records.device
+    pose_out = torch.empty((B, n, 3, 4), dtype=torch.float64, device=dev)
+    class_out = torch.empty((B, n), dtype=torch.int32, device=dev)
+    inliers_out = torch.empty((B, n), dtype=torch.int32, device=dev)
+    check("pcnn_pose2d_round_fwd",
+          lib().pcnn_pose2d_round_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(intrinsics), _ptr(hyp_pose), _ptr(hyp_class),
+                                      B, H, W, C, n, int(round), int(pixel_batch), int(max_pixels), float(inlier_threshold),
+                                      _ptr(pose_out), _ptr(class_out), _ptr(inliers_out), _stream(records)))
+    return pose_out, class_out, inliers_out
+
+
+def estimate_poses_2d(label_2d, vertex_pred, extents, intrinsics, seed=0, streams=None, hypotheses=256, pixel_batch=1000,
+                      max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=10.0, min_dist2d=10.0, min_dist3d=0.01,
+                      min_pixels=10, max_attempts=1024, workspace=None):
+    """`Synthesizer::estimatePose2D` (lib/synthesize/synthesize.cpp:1571-1767) for a batch, three launches and no
+    synchronisation, no depth frame: label_2d int32 [B,H,W], vertex_pred f32 [B,H,W,3C] (the `vertex_reg_3d` network's
+    object coordinates, scaled into [0, 1] per extent), extents f32 [C,3], intrinsics f32 [B,4] rows (fx, fy, px, py).
+    seed, streams and the return value as in `estimate_poses_3d`: device tensors (poses f32 [B,C,3,4], poses64 f64
+    [B,C,3,4], inliers, ref_steps, num_hyps int32 [B,C]); a class without hypothesis is all zero. inlier_threshold and
+    min_dist2d are in pixels, min_dist3d in metres. min_pixels only gated the reference's nlopt polish, which is not built:
+    accepted and unused. Deviations from the reference: DESIGN.md 3.7c."""
+    label_2d, vertex_pred, extents, intrinsics, B, H, W, C = _pose2d_frames(label_2d, vertex_pred, extents, intrinsics)
+    dev = label_2d.device
+    streams = _pose3d_streams(streams, B, dev)
+    s0, s1 = _pose3d_seed(seed)
+    int(min_pixels)
+    nbytes = c_size_t()
+    check("pcnn_pose2d_workspace_bytes", lib().pcnn_pose2d_workspace_bytes(B, H, W, C, int(hypotheses), ctypes.byref(nbytes)))
+    ws = (workspace or _ws(dev, "pose2d")).get(nbytes.value, dev)
+    poses64 = torch.empty((B, C, 3, 4), dtype=torch.float64, device=dev)
+    poses = torch.empty((B, C, 3, 4), dtype=torch.float32, device=dev)
+    inliers = torch.empty((B, C), dtype=torch.int32, device=dev)
+    ref_steps = torch.empty((B, C), dtype=torch.int32, device=dev)
+    num_hyps = torch.empty((B, C), dtype=torch.int32, device=dev)
+    check("pcnn_pose2d_estimate_fwd",
+          lib().pcnn_pose2d_estimate_fwd(_ptr(label_2d), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics), _ptr(streams), s0, s1,
+                                         B, H, W, C, int(hypotheses), int(pixel_batch), int(max_pixels), int(ref_it), int(min_area),
+                                         float(inlier_threshold), float(min_dist2d), float(min_dist3d), int(max_attempts),
+                                         _ptr(poses64), _ptr(poses), _ptr(inliers), _ptr(ref_steps), _ptr(num_hyps), _ptr(ws),
+                                         nbytes.value, _stream(poses)))
     return poses, poses64, inliers, ref_steps, num_hyps
