@@ -1,7 +1,5 @@
-"""ctypes binding of libposecnn_hip.so (the C-ABI declared in include/posecnn_hip.h, include/posecnn_hip_train.h,
-include/posecnn_hip_frontend.h, include/posecnn_hip_synth.h, include/posecnn_hip_augment.h, include/posecnn_hip_loss.h,
-include/posecnn_hip_vertex_loss.h, include/posecnn_hip_trunk_train.h, include/posecnn_hip_pose3d.h, include/posecnn_hip_pose2d.h and
-include/posecnn_hip_wino_packed.h).
+"""ctypes binding of libposecnn_hip.so: the C-ABI is what the headers under include/ declare, and the ctypes signatures
+are derived from their prototypes when the library is first loaded (`BINDINGS`), not repeated here.
 
 This is the Python-side analogue of the reference's ``tf.load_op_library('<op>.so')`` stubs
 (lib/hough_voting_gpu_layer/hough_voting_gpu_op.py:4-7 and siblings). The library is built
@@ -9,8 +7,10 @@ in-tree by ``__graft_entry__.build()`` / ``make -C posecnn_amd/csrc``. There is 
 if the shared object is missing or an entry point fails, the call raises.
 """
 import ctypes
+import glob
 import os
-from ctypes import (POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p)
+import re
+from ctypes import (POINTER, c_char_p, c_float, c_int, c_int64, c_long, c_size_t, c_uint32, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libposecnn_hip.so")
@@ -26,189 +26,95 @@ HOUGH_ROWS_CAPACITY = MAX_ROI * 9
 VERTEX_CHANNELS = 3
 POSE_CHANNELS = 4
 
-_P = c_void_p
+INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
-# name -> (restype, argtypes); must list every symbol of include/posecnn_hip.h
-SIGNATURES = {
-    "pcnn_abi_version": (c_int, []),
-    "pcnn_last_error_string": (c_char_p, []),
-    "pcnn_status_string": (c_char_p, [c_int]),
-    "pcnn_hough_voting_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_float, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_hough_voting_debug_layout": (c_int, [c_int, c_int, c_int, c_int, c_float, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_hough_voting_fwd": (c_int, [_P, _P, _P, _P, _P,
-                                      c_int, c_int, c_int, c_int, c_int, c_int,
-                                      c_int, c_float, c_float, c_int, c_float, c_int, c_int, c_int,
-                                      _P, _P, _P, _P, _P, _P,
-                                      _P, c_size_t, _P]),
-    "pcnn_hough_voting_lowres_fwd": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P,
-                                             c_int, c_int, c_int, c_int, c_int, c_int,
-                                             c_int, c_float, c_float, c_int, c_float, c_int, c_int, c_int,
-                                             _P, _P, _P, _P, _P, _P,
-                                             _P, c_size_t, _P]),
-    "pcnn_deconv_bilinear_bwd": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_smooth_l1_vertex_workspace_bytes": (c_int, [_P]),
-    "pcnn_smooth_l1_vertex_fwd": (c_int, [_P, _P, _P, c_int64, c_float, _P, _P, c_size_t, _P]),
-    "pcnn_smooth_l1_vertex_bwd": (c_int, [_P, _P, _P, _P, _P, c_int64, c_float, _P, _P]),
-    "pcnn_winograd_input_fwd": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_winograd_output_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_winograd43_input_fwd": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_winograd43_output_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_winograd43_output_both_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcnn_fc_rows_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
-    "pcnn_fc_rows_cols_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcnn_fc_rows_split_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcnn_fc_rows_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_fc_skinny_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_int)]),
-    "pcnn_fc_skinny_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P, c_int, _P]),
-    "pcnn_head_lowres_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcnn_head_lowres_mfma_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcnn_det_assemble_packed_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P]),
-    "pcnn_pose_l2_normalize_fwd": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
-    "pcnn_det_assemble_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
-    "pcnn_winograd43_conv_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "pcnn_winograd43_conv_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_conv3x3_c3_winograd43_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_conv3x3_c3_winograd43_raw_fwd": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_conv1_1_conv1_2_fused_fwd": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_conv1_1_conv1_2_fused_raw_fwd": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_conv3x3_c3_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_bias_relu_pool2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_hough_voting_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
-    "pcnn_roi_pool_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_int, c_int, c_float, c_int, _P, _P, _P]),
-    "pcnn_roi_pool_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_int, c_int, c_float, c_int, _P, _P]),
-    "pcnn_roi_pool_add2_fwd": (c_int, [_P, c_int, c_int, c_float, _P, c_int, c_int, c_float,
-                                       _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcnn_roi_pool_add2_live_fwd": (c_int, [_P, c_int, c_int, c_float, _P, c_int, c_int, c_float,
-                                            _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcnn_hard_label_fwd": (c_int, [_P, _P, c_int64, c_int, c_float, _P, _P]),
-    "pcnn_hard_label_bwd": (c_int, [_P, _P, c_int64, c_int, _P]),
-    "pcnn_average_distance_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_average_distance_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P,
-                                          _P, _P, _P, c_size_t, _P]),
-    "pcnn_average_distance_bwd": (c_int, [_P, _P, c_int, c_int, _P, _P]),
-    "pcnn_backproject_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
-                                     c_int, c_int, c_int, c_float, _P, _P, _P, _P]),
-    "pcnn_backproject_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_backproject_ws_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
-                                        c_int, c_int, c_int, c_float, _P, _P, _P, _P, c_size_t, _P]),
-    "pcnn_backproject_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    "pcnn_softmax_argmax_fwd": (c_int, [_P, c_int64, c_int, _P, _P, _P]),
-    "pcnn_deconv_bilinear_fwd": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P]),
-    "pcnn_bias_act_fwd": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P]),
-    "pcnn_upscore_softmax_argmax_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcnn_upscore_softmax_argmax_hard_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_float, _P, _P]),
-    "pcnn_icp_backproject_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, _P, _P]),
-    "pcnn_icp_refine_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_icp_refine_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
-                                    c_int, _P, _P, _P, c_size_t, _P]),
-    "pcnn_render_mesh_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_render_mesh_fwd": (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
-                                     c_float, _P, _P, _P, _P, c_size_t, _P]),
-    "pcnn_icp_center_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_icp_center_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
-    "pcnn_icp_score_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_icp_score_fwd": (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_float, c_float, c_float, c_float, c_float, _P, _P, c_size_t, _P]),
-    "pcnn_icp_polish_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, _P, _P, _P]),
-    "pcnn_crc32c": (ctypes.c_uint32, [_P, c_size_t, ctypes.c_uint32]),
-    "pcnn_profile_enable": (c_int, [c_int]),
-    "pcnn_profile_reset": (c_int, []),
-    "pcnn_profile_report": (ctypes.c_long, [ctypes.c_char_p, ctypes.c_long]),
-}
+# ---- the headers are the one statement of the C-ABI: every `ret pcnn_name(params);` in them is bound from its own text ----
+# The grammar is closed: what it does not name raises, nothing falls back to void*.
+_RESTYPES = {"int": c_int, "long": c_long, "uint32_t": c_uint32, "const char*": c_char_p}
+_SCALARS = {"int": c_int, "long": c_long, "float": c_float, "size_t": c_size_t, "int64_t": c_int64, "uint32_t": c_uint32,
+            "uint64_t": c_uint64}
+_POINTERS = {"size_t": POINTER(c_size_t), "int": POINTER(c_int), "char": c_char_p}   # every other pointer: void*
+
+BINDINGS = {}   # header basename -> {symbol: (restype, argtypes)} in header order; filled by the first lib() call
 
 
-# the training-side entries of include/posecnn_hip_train.h (same library, same ABI version)
-TRAIN_SIGNATURES = {
-    "pcnn_vertex_targets_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "pcnn_smooth_l1_vertex_gt_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
-    "pcnn_smooth_l1_vertex_gt_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P]),
-}
+def _strip_comments(text):
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
 
-# the input front-end entries of include/posecnn_hip_frontend.h (same library, same ABI version)
-FRONTEND_SIGNATURES = {
-    "pcnn_depth_normals_fwd": (c_int, [_P, _P, c_float, _P, c_int, c_int, c_int, c_float, _P, _P]),
-    "pcnn_bilateral_u8c3_fwd": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
-    "pcnn_normal_image_fwd": (c_int, [_P, _P, c_float, _P, c_int, c_int, c_int, c_float, c_int, _P, _P, c_int, _P, _P]),
-}
 
-# the synthetic-scene entries of include/posecnn_hip_synth.h (same library, same ABI version)
-SYNTH_SIGNATURES = {
-    "pcnn_synth_scene_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_synth_scene_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, c_size_t, _P, _P, _P, c_int, _P, _P,
-                                     c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_int,
-                                     _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-}
+def _argtype(param, where):
+    if "(" in param or "[" in param:
+        raise ValueError("%s: array and function-pointer parameters are not part of the C-ABI" % where)
+    tokens = [t for t in re.findall(r"\w+|\*", param) if t != "const"]
+    stars = tokens.count("*")
+    if stars > 1:
+        raise ValueError("%s: pointer to pointer" % where)
+    if stars:
+        base, name = tokens[:tokens.index("*")], tokens[tokens.index("*") + 1:]
+        if not base or len(name) > 1:
+            raise ValueError("%s: not `type* [name]`" % where)
+        return _POINTERS.get(" ".join(base), c_void_p)
+    base = " ".join(tokens[:-1] if len(tokens) > 1 else tokens)   # the last word is the parameter's name
+    if base not in _SCALARS:
+        raise ValueError("%s: scalar type '%s' is not one of %s" % (where, base, sorted(_SCALARS)))
+    return _SCALARS[base]
 
-# the training-augmentation entries of include/posecnn_hip_augment.h (same library, same ABI version)
-AUGMENT_SIGNATURES = {
-    "pcnn_augment_frames_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_augment_frames_fwd": (c_int, [_P, c_int, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-}
 
-# the training label-head loss entries of include/posecnn_hip_loss.h (same library, same ABI version)
-LOSS_SIGNATURES = {
-    "pcnn_label_head_loss_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_label_head_loss_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P,
-                                         c_size_t, _P]),
-    "pcnn_label_head_loss_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
-                                         c_size_t, _P]),
-}
+def parse_header(header, text):
+    """The prototypes of one header's text -> {symbol: (restype, argtypes)}; ValueError names header, symbol and parameter."""
+    text = re.sub(r"^[ \t]*#.*$", "", _strip_comments(text), flags=re.M)
+    found = {}
+    for m in re.finditer(r"\b(pcnn_\w+)\s*\(", text):
+        name, depth, end = m.group(1), 1, m.end()
+        while depth and end < len(text):
+            depth += {"(": 1, ")": -1}.get(text[end], 0)
+            end += 1
+        if depth or not re.match(r"\s*;", text[end:]):
+            raise ValueError("%s: %s: not a prototype `ret %s(params);`" % (header, name, name))
+        ret = re.sub(r"\s*\*\s*", "*", " ".join(re.split(r"[;{}]", text[:m.start()])[-1].split()))
+        if ret not in _RESTYPES:
+            raise ValueError("%s: %s: return type '%s' is not one of %s" % (header, name, ret, sorted(_RESTYPES)))
+        if name in found:
+            raise ValueError("%s: %s is declared twice" % (header, name))
+        params, depth = [""], 0
+        for ch in text[m.end():end - 1]:
+            depth += {"(": 1, "[": 1, ")": -1, "]": -1}.get(ch, 0)
+            if ch == "," and not depth:
+                params.append("")
+            else:
+                params[-1] += ch
+        params = [" ".join(p.split()) for p in params]
+        found[name] = (_RESTYPES[ret], [] if params == ["void"] else
+                       [_argtype(p, "%s: %s: parameter %d '%s'" % (header, name, i + 1, p)) for i, p in enumerate(params)])
+    return found
 
-# the training vertex-head loss entries of include/posecnn_hip_vertex_loss.h (same library, same ABI version)
-VERTEX_LOSS_SIGNATURES = {
-    "pcnn_vertex_head_loss_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_vertex_head_loss_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P,
-                                          c_size_t, _P]),
-    "pcnn_vertex_head_loss_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                          _P, _P, _P, c_size_t, _P]),
-}
 
-# the training trunk-epilogue entries of include/posecnn_hip_trunk_train.h (same library, same ABI version)
-TRUNK_TRAIN_SIGNATURES = {
-    "pcnn_bias_relu_pool2_train_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_bias_relu_train_workspace_bytes": (c_int, [c_int64, c_int, POINTER(c_size_t)]),
-    "pcnn_bias_relu_pool2_train_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcnn_bias_relu_pool2_train_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "pcnn_bias_relu_train_bwd": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-}
+def parse_headers(texts):
+    """[(header basename, text), ...] -> {basename: parse_header(...)} in the given order; a symbol in two headers raises."""
+    out, owner = {}, {}
+    for header, text in texts:
+        out[header] = parse_header(header, text)
+        for name in out[header]:
+            if name in owner:
+                raise ValueError("%s: %s is already declared in %s" % (header, name, owner[name]))
+            owner[name] = header
+    return out
 
-# the 3-D vertex route's pose entries of include/posecnn_hip_pose3d.h (same library, same ABI version)
-POSE3D_SIGNATURES = {
-    "pcnn_pose3d_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_pose3d_prepare_fwd": (c_int, [_P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcnn_pose3d_sample_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                       c_float, c_float, _P, _P, _P, _P, _P]),
-    "pcnn_pose3d_round_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                      _P, _P, _P, _P]),
-    "pcnn_pose3d_estimate_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_uint64, c_uint64, c_int, c_int, c_int, c_int,
-                                         c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
-                                         _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-}
 
-# the colour-only pose entries of include/posecnn_hip_pose2d.h (same library, same ABI version)
-POSE2D_SIGNATURES = {
-    "pcnn_pose2d_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
-    "pcnn_pose2d_prepare_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "pcnn_pose2d_sample_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                       c_float, c_float, c_float, _P, _P, _P, _P, _P]),
-    "pcnn_pose2d_round_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                      _P, _P, _P, _P]),
-    "pcnn_pose2d_estimate_fwd": (c_int, [_P, _P, _P, _P, _P, c_uint64, c_uint64, c_int, c_int, c_int, c_int,
-                                         c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int,
-                                         _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-}
+def header_texts():
+    """[(basename, text)] of every include/*.h, sorted by name."""
+    return [(os.path.basename(p), open(p).read()) for p in sorted(glob.glob(os.path.join(INCLUDE_DIR, "*.h")))]
 
-# the packed-filter route of the Winograd trunk kernel, include/posecnn_hip_wino_packed.h (same library, same ABI version)
-WINO_PACKED_SIGNATURES = {
-    "pcnn_winograd43_pack_filters_fwd": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
-    "pcnn_winograd43_conv_packed_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-}
+
+def header_abi_version(texts=None):
+    """PCNN_ABI_VERSION as include/posecnn_hip.h defines it."""
+    text = dict(header_texts() if texts is None else texts)["posecnn_hip.h"]
+    return int(re.search(r"^[ \t]*#[ \t]*define[ \t]+PCNN_ABI_VERSION[ \t]+(\d+)[ \t]*$", _strip_comments(text), flags=re.M).group(1))
 
 
 def profile_enable(on=True):
     """Bracket every library kernel launch with HIP events on its launch stream."""
-    check("pcnn_profile_enable", lib().pcnn_profile_enable(1 if on else 0))
+    call("pcnn_profile_enable", 1 if on else 0)
 
 
 def profile_report(reset=True):
@@ -250,15 +156,16 @@ def lib():
         # (round 6: `build()` followed by `smoke()` in one process did exactly that). So torch's goes in first, always.
         import torch  # noqa: F401
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(FRONTEND_SIGNATURES.items()) +\
-                list(SYNTH_SIGNATURES.items()) + list(AUGMENT_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) +\
-                list(VERTEX_LOSS_SIGNATURES.items()) + list(TRUNK_TRAIN_SIGNATURES.items()) + list(POSE3D_SIGNATURES.items()) +\
-                list(POSE2D_SIGNATURES.items()) + list(WINO_PACKED_SIGNATURES.items()):
-            fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
-            fn.restype = res
-            fn.argtypes = args
-        if handle.pcnn_abi_version() != 2:
+        texts = header_texts()
+        bindings = parse_headers(texts)
+        for table in bindings.values():
+            for name, (res, args) in table.items():
+                fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly
+                fn.restype = res
+                fn.argtypes = args
+        if handle.pcnn_abi_version() != header_abi_version(texts):
             raise RuntimeError("libposecnn_hip.so ABI version mismatch")
+        BINDINGS.update(bindings)
         _lib = handle
     return _lib
 
@@ -271,3 +178,8 @@ def check(fn_name, status):
             # the reference raises InvalidArgument for the same conditions (OP_REQUIRES)
             raise ValueError("%s: %s" % (fn_name, msg))
         raise PoseCNNHipError(fn_name, status, msg)
+
+
+def call(name, *args):
+    """Call the entry `name` of the library (AttributeError if it has none) and pass its status through `check`."""
+    check(name, getattr(lib(), name)(*args))

@@ -20,14 +20,18 @@ frame run phase by phase on their own streams.
 No assimp here: meshes are Wavefront OBJ read by `Mesh.load_obj` (positions, faces, optional normals; smooth normals are
 generated like aiProcess_GenSmoothNormals when the file has none).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import ops
 from ._lib import check, lib
 from .pose_error import quat2mat
+
+
+def call(name, *args):
+    """`_lib.call` with the handle taken from this module's `lib` (see ops.call)."""
+    check(name, getattr(lib(), name)(*args))
+
 
 Z_NEAR, Z_FAR = 0.25, 6.0          # lib/fcn/test.py:1905-1906
 ERROR_THRESHOLD = 0.01             # lib/fcn/test.py:1909
@@ -40,9 +44,8 @@ def backproject(depth, label, obj_id, K, factor_depth):
     lab = ops._dev(label, "label", torch.int32) if label is not None else None
     H, W = depth.shape
     out = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
-    check("pcnn_icp_backproject_fwd",
-          lib().pcnn_icp_backproject_fwd(ops._ptr(depth), ops._ptr(lab), H, W, int(obj_id), float(factor_depth), float(K[0, 0]), float(K[1, 1]),
-                                         float(K[0, 2]), float(K[1, 2]), ops._ptr(out), ops._stream(depth)))
+    call("pcnn_icp_backproject_fwd", ops._ptr(depth), ops._ptr(lab), H, W, int(obj_id), float(factor_depth), float(K[0, 0]),
+         float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), ops._ptr(out), ops._stream(depth))
     return out
 
 
@@ -59,13 +62,10 @@ def icp(live_vertices, pred_vertices, pred_normals, K, depth_range=(Z_NEAR, Z_FA
     N, H, W, _ = live.shape
     update = torch.empty((N, 3, 4), dtype=torch.float64, device=live.device)
     stats = torch.zeros((N, max(iterations, 1), 2), dtype=torch.float32, device=live.device) if want_stats else None
-    nbytes = ctypes.c_size_t()
-    check("pcnn_icp_refine_workspace_bytes", lib().pcnn_icp_refine_workspace_bytes(N, H, W, ctypes.byref(nbytes)))
-    ws = ops._ws(live.device, "icp").get(nbytes.value, live.device)
-    check("pcnn_icp_refine_fwd",
-          lib().pcnn_icp_refine_fwd(ops._ptr(live), ops._ptr(pv), ops._ptr(pn), N, H, W, int(pv.shape[3]), float(K[0, 0]), float(K[1, 1]),
-                                    float(K[0, 2]), float(K[1, 2]), float(depth_range[0]), float(depth_range[1]), float(max_error),
-                                    int(iterations), ops._ptr(update), ops._ptr(stats), ops._ptr(ws), nbytes.value, ops._stream(live)))
+    ws, nbytes = ops._workspace(live.device, "icp", "pcnn_icp_refine_workspace_bytes", N, H, W)
+    call("pcnn_icp_refine_fwd", ops._ptr(live), ops._ptr(pv), ops._ptr(pn), N, H, W, int(pv.shape[3]), float(K[0, 0]),
+         float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), float(depth_range[0]), float(depth_range[1]), float(max_error),
+         int(iterations), ops._ptr(update), ops._ptr(stats), ops._ptr(ws), nbytes, ops._stream(live))
     return (update, stats) if want_stats else update
 
 
@@ -160,15 +160,11 @@ def render(mesh, poses, K, height, width, depth_range=(Z_NEAR, Z_FAR), model_ind
     out = {}
     for key, ch in (("vertices", 4), ("normals", 4), ("canonical", 3)):
         out[key] = torch.empty((N, height, width, ch), dtype=torch.float32, device=dev) if key in want else None
-    nbytes = ctypes.c_size_t()
-    check("pcnn_render_mesh_workspace_bytes", lib().pcnn_render_mesh_workspace_bytes(N, height, width, ctypes.byref(nbytes)))
-    ws = ops._ws(dev, "render").get(nbytes.value, dev)
-    check("pcnn_render_mesh_fwd",
-          lib().pcnn_render_mesh_fwd(ops._ptr(mesh.vertices), ops._ptr(mesh.normals), ops._ptr(mesh.faces), mesh.vertices.shape[0],
-                                     mesh.faces.shape[0], ops._ptr(P), N, height, width, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]),
-                                     float(K[1, 2]), float(depth_range[0]), float(depth_range[1]), float(model_index),
-                                     ops._ptr(out["vertices"]), ops._ptr(out["normals"]), ops._ptr(out["canonical"]), ops._ptr(ws),
-                                     nbytes.value, ops._stream(mesh.vertices)))
+    ws, nbytes = ops._workspace(dev, "render", "pcnn_render_mesh_workspace_bytes", N, height, width)
+    call("pcnn_render_mesh_fwd", ops._ptr(mesh.vertices), ops._ptr(mesh.normals), ops._ptr(mesh.faces), mesh.vertices.shape[0],
+         mesh.faces.shape[0], ops._ptr(P), N, height, width, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]),
+         float(depth_range[0]), float(depth_range[1]), float(model_index), ops._ptr(out["vertices"]), ops._ptr(out["normals"]),
+         ops._ptr(out["canonical"]), ops._ptr(ws), nbytes, ops._stream(mesh.vertices))
     return {k: v for k, v in out.items() if v is not None}
 
 
@@ -185,13 +181,9 @@ def center(label, live_vertices, canonical, pred_vertices, pred_normals, obj_id,
         raise ValueError("label [H,W], live / canonical [H,W,3], pred_* [H,W,3|4]")
     sums = torch.empty((5,), dtype=torch.float64, device=lab.device)
     mask = torch.empty((H, W), dtype=torch.uint8, device=lab.device)
-    nbytes = ctypes.c_size_t()
-    check("pcnn_icp_center_workspace_bytes", lib().pcnn_icp_center_workspace_bytes(H, W, ctypes.byref(nbytes)))
-    ws = ops._ws(lab.device, "icp_center").get(nbytes.value, lab.device)
-    check("pcnn_icp_center_fwd",
-          lib().pcnn_icp_center_fwd(ops._ptr(lab), ops._ptr(live), ops._ptr(can), ops._ptr(pv), ops._ptr(pn), int(pv.shape[2]), H, W,
-                                    int(obj_id), float(max_error), ops._ptr(sums), ops._ptr(mask), ops._ptr(ws), nbytes.value,
-                                    ops._stream(lab)))
+    ws, nbytes = ops._workspace(lab.device, "icp_center", "pcnn_icp_center_workspace_bytes", H, W)
+    call("pcnn_icp_center_fwd", ops._ptr(lab), ops._ptr(live), ops._ptr(can), ops._ptr(pv), ops._ptr(pn), int(pv.shape[2]), H, W,
+         int(obj_id), float(max_error), ops._ptr(sums), ops._ptr(mask), ops._ptr(ws), nbytes, ops._stream(lab))
     return sums, mask
 
 
@@ -206,13 +198,9 @@ def score(live_vertices, canonical, mask, hypotheses, K, radius=0.01):
                           dtype=torch.float32).to(live.device).reshape(-1, 12).contiguous()
     M = hyp.shape[0]
     hits = torch.empty((M,), dtype=torch.int32, device=live.device)
-    nbytes = ctypes.c_size_t()
-    check("pcnn_icp_score_workspace_bytes", lib().pcnn_icp_score_workspace_bytes(M, H, W, ctypes.byref(nbytes)))
-    ws = ops._ws(live.device, "icp_score").get(max(nbytes.value, 4), live.device)
-    check("pcnn_icp_score_fwd",
-          lib().pcnn_icp_score_fwd(ops._ptr(live), ops._ptr(can), ops._ptr(msk), H, W, ops._ptr(hyp), M, float(K[0, 0]), float(K[1, 1]),
-                                   float(K[0, 2]), float(K[1, 2]), float(radius), ops._ptr(hits), ops._ptr(ws), nbytes.value,
-                                   ops._stream(live)))
+    ws, nbytes = ops._workspace(live.device, "icp_score", "pcnn_icp_score_workspace_bytes", M, H, W, at_least=4)
+    call("pcnn_icp_score_fwd", ops._ptr(live), ops._ptr(can), ops._ptr(msk), H, W, ops._ptr(hyp), M, float(K[0, 0]), float(K[1, 1]),
+         float(K[0, 2]), float(K[1, 2]), float(radius), ops._ptr(hits), ops._ptr(ws), nbytes, ops._stream(live))
     return hits
 
 
@@ -228,9 +216,8 @@ def polish_async(label, live_vertices, pred_vertices, obj_id, depth_range=(Z_NEA
         raise ValueError("label [H,W], live [H,W,3], pred_vertices [H,W,3|4]")
     x = torch.empty((7,), dtype=torch.float64, device=lab.device)
     info = torch.empty((2,), dtype=torch.float64, device=lab.device)
-    check("pcnn_icp_polish_fwd",
-          lib().pcnn_icp_polish_fwd(ops._ptr(lab), ops._ptr(live), ops._ptr(pv), int(pv.shape[2]), H, W, int(obj_id), float(depth_range[0]),
-                                    float(depth_range[1]), int(max_evaluations), ops._ptr(x), ops._ptr(info), ops._stream(lab)))
+    call("pcnn_icp_polish_fwd", ops._ptr(lab), ops._ptr(live), ops._ptr(pv), int(pv.shape[2]), H, W, int(obj_id),
+         float(depth_range[0]), float(depth_range[1]), int(max_evaluations), ops._ptr(x), ops._ptr(info), ops._stream(lab))
     return x, info
 
 

@@ -14,7 +14,7 @@ import numpy as np
 
 import torch
 
-from . import _lib
+from . import _lib  # noqa: F401  (tests and tools reach the binding as ops._lib)
 from ._lib import HOUGH_ROWS_CAPACITY, MAX_ROI, POSE_CHANNELS, VERTEX_CHANNELS, check, lib
 
 __all__ = [
@@ -32,6 +32,12 @@ __all__ = [
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
 LABEL_THRESHOLD = 500   # hough_voting_gpu_op.cc:357
+
+
+def call(name, *args):
+    """`_lib.call` with the handle taken from THIS module's `lib`: the memory-contract tests stand a recorder in for it,
+    module by module (icp.py and synthesize.py have the same two lines for the same reason)."""
+    check(name, getattr(lib(), name)(*args))
 
 
 def _dev(t, name, dtype):
@@ -81,6 +87,17 @@ def _ws(device, key):
     return _default_ws[k]
 
 
+def _workspace(device, key, query, *dims, workspace=None, at_least=1):
+    """The scratch of one entry: ask its `query` (a pcnn_*_workspace_bytes entry, called with `dims`) for the size and fetch
+    max(that, at_least) bytes from `workspace` (a caller's Workspace) or from this stream's own under `key`.
+    -> (buffer, bytes asked for). at_least=0 is for the entries that take NULL when they need nothing: the buffer is then
+    None and no Workspace is touched."""
+    nbytes = c_size_t(0)
+    call(query, *dims, ctypes.byref(nbytes))
+    need = max(nbytes.value, at_least)
+    return ((workspace or _ws(device, key)).get(need, device) if need else None), nbytes.value
+
+
 # ------------------------------------------------------------------------------------------------
 def hough_rows_capacity(batch, is_train, rois_per_image=0):
     """Rows each Hough output needs: the reference's scratch size MAX_ROI * 9
@@ -124,11 +141,8 @@ def _hough_common(label_2d, field, extents, meta_data, poses, threshold, skip_pi
             raise ValueError("poses (gt) must be [N,13]")
         num_gt = gt.shape[0]
     dev = label_2d.device
-    nbytes = c_size_t(0)
-    check("pcnn_hough_voting_workspace_bytes",
-          lib().pcnn_hough_voting_workspace_bytes(B, H, W, C, float(threshold), int(skip_pixels),
-                                                  int(rois_per_image), ctypes.byref(nbytes)))
-    ws = (workspace or _ws(dev, "hough")).get(nbytes.value, dev)
+    ws, _ = _workspace(dev, "hough", "pcnn_hough_voting_workspace_bytes", B, H, W, C, float(threshold), int(skip_pixels),
+                       int(rois_per_image), workspace=workspace)
     if out is None:
         cap = hough_rows_capacity(B, is_train, rois_per_image)
         out = (torch.empty((cap, 7), dtype=torch.float32, device=dev),
@@ -157,15 +171,10 @@ def hough_voting_gpu_padded(label_2d, vertex_pred, extents, meta_data, poses, is
         label_2d, vertex_pred, extents, meta_data, poses, threshold, skip_pixels, workspace, out, None,
         is_train, rois_per_image)
     top_box, top_pose, top_target, top_weight, top_domain, num_rois = out
-    check("pcnn_hough_voting_fwd",
-          lib().pcnn_hough_voting_fwd(_ptr(label_2d), _ptr(vertex_pred), _ptr(extents), _ptr(meta_data), _ptr(gt),
-                                      B, H, W, C, num_meta, num_gt,
-                                      int(is_train), float(threshold), float(per_threshold), int(skip_pixels),
-                                      float(inlier_threshold), int(label_threshold),
-                                      int(rois_per_image), int(top_box.shape[0]),
-                                      _ptr(top_box), _ptr(top_pose), _ptr(top_target), _ptr(top_weight),
-                                      _ptr(top_domain), _ptr(num_rois),
-                                      _ptr(ws), ws.numel(), _stream(label_2d)))
+    call("pcnn_hough_voting_fwd", _ptr(label_2d), _ptr(vertex_pred), _ptr(extents), _ptr(meta_data), _ptr(gt), B, H, W, C, num_meta,
+         num_gt, int(is_train), float(threshold), float(per_threshold), int(skip_pixels), float(inlier_threshold),
+         int(label_threshold), int(rois_per_image), int(top_box.shape[0]), _ptr(top_box), _ptr(top_pose), _ptr(top_target),
+         _ptr(top_weight), _ptr(top_domain), _ptr(num_rois), _ptr(ws), ws.numel(), _stream(label_2d))
     return out
 
 
@@ -184,16 +193,11 @@ def hough_voting_gpu_lowres_padded(label_2d, z, bias, kernel, stride, extents, m
     if bias.numel() != VERTEX_CHANNELS * C:
         raise ValueError("bias must be [3*num_classes]")
     top_box, top_pose, top_target, top_weight, top_domain, num_rois = out
-    check("pcnn_hough_voting_lowres_fwd",
-          lib().pcnn_hough_voting_lowres_fwd(_ptr(label_2d), _ptr(z), _ptr(bias), int(kernel), int(stride),
-                                             _ptr(extents), _ptr(meta_data), _ptr(gt),
-                                             B, H, W, C, num_meta, num_gt,
-                                             int(is_train), float(threshold), float(per_threshold), int(skip_pixels),
-                                             float(inlier_threshold), int(label_threshold),
-                                             int(rois_per_image), int(top_box.shape[0]),
-                                             _ptr(top_box), _ptr(top_pose), _ptr(top_target), _ptr(top_weight),
-                                             _ptr(top_domain), _ptr(num_rois),
-                                             _ptr(ws), ws.numel(), _stream(label_2d)))
+    call("pcnn_hough_voting_lowres_fwd", _ptr(label_2d), _ptr(z), _ptr(bias), int(kernel), int(stride), _ptr(extents),
+         _ptr(meta_data), _ptr(gt), B, H, W, C, num_meta, num_gt, int(is_train), float(threshold), float(per_threshold),
+         int(skip_pixels), float(inlier_threshold), int(label_threshold), int(rois_per_image), int(top_box.shape[0]), _ptr(top_box),
+         _ptr(top_pose), _ptr(top_target), _ptr(top_weight), _ptr(top_domain), _ptr(num_rois), _ptr(ws), ws.numel(),
+         _stream(label_2d))
     return out
 
 
@@ -206,7 +210,7 @@ def hough_voting_grad(label_2d, vertex_pred):
     dev = vertex_pred.device
     gl = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     gv = torch.empty((B, H, W, VERTEX_CHANNELS * C), dtype=torch.float32, device=dev)
-    check("pcnn_hough_voting_bwd", lib().pcnn_hough_voting_bwd(_ptr(gl), _ptr(gv), B, H, W, C, _stream(gv)))
+    call("pcnn_hough_voting_bwd", _ptr(gl), _ptr(gv), B, H, W, C, _stream(gv))
     return gl, gv
 
 
@@ -257,10 +261,8 @@ class _RoiPoolFn(torch.autograd.Function):
         Cout = 1 if pool_channel else C
         top = torch.empty((R, pooled_height, pooled_width, Cout), dtype=torch.float32, device=data.device)
         argmax = torch.empty((R, pooled_height, pooled_width, Cout), dtype=torch.int32, device=data.device)
-        check("pcnn_roi_pool_fwd",
-              lib().pcnn_roi_pool_fwd(_ptr(data), _ptr(rois), B, H, W, C, R, cols, int(pooled_height),
-                                      int(pooled_width), float(spatial_scale), int(pool_channel),
-                                      _ptr(top), _ptr(argmax), _stream(data)))
+        call("pcnn_roi_pool_fwd", _ptr(data), _ptr(rois), B, H, W, C, R, cols, int(pooled_height), int(pooled_width),
+             float(spatial_scale), int(pool_channel), _ptr(top), _ptr(argmax), _stream(data))
         ctx.save_for_backward(rois, argmax)
         ctx.cfg = (B, H, W, C, R, cols, int(pooled_height), int(pooled_width), float(spatial_scale), int(pool_channel))
         ctx.mark_non_differentiable(argmax)
@@ -272,9 +274,8 @@ class _RoiPoolFn(torch.autograd.Function):
         B, H, W, C, R, cols, PH, PW, scale, pc = ctx.cfg
         grad_top = grad_top.contiguous()
         bottom = torch.empty((B, H, W, C), dtype=torch.float32, device=grad_top.device)
-        check("pcnn_roi_pool_bwd",
-              lib().pcnn_roi_pool_bwd(_ptr(grad_top), _ptr(rois), _ptr(argmax), B, H, W, C, R, cols, PH, PW,
-                                      scale, pc, _ptr(bottom), _stream(grad_top)))
+        call("pcnn_roi_pool_bwd", _ptr(grad_top), _ptr(rois), _ptr(argmax), B, H, W, C, R, cols, PH, PW, scale, pc, _ptr(bottom),
+             _stream(grad_top))
         return bottom, None, None, None, None, None
 
 
@@ -314,11 +315,9 @@ def roi_pool_add2(data_a, scale_a, data_b, scale_b, rois, pooled_height=7, poole
         if tuple(out.shape) != (R, pooled_height, pooled_width, C):
             raise ValueError("out must be [R, PH, PW, C]")
     name = "pcnn_roi_pool_add2_live_fwd" if dead_rows == "keep" else "pcnn_roi_pool_add2_fwd"
-    check(name,
-          getattr(lib(), name)(_ptr(data_a), Ha, Wa, float(scale_a), _ptr(data_b), Hb, Wb, float(scale_b),
-                               _ptr(rois), B, C, R, cols, int(pooled_height), int(pooled_width),
-                               _ptr(_dev(num_rows, "num_rows", torch.int32) if num_rows is not None else None),
-                               _ptr(out), _stream(data_a)))
+    call(name, _ptr(data_a), Ha, Wa, float(scale_a), _ptr(data_b), Hb, Wb, float(scale_b), _ptr(rois), B, C, R, cols,
+         int(pooled_height), int(pooled_width), _ptr(_dev(num_rows, "num_rows", torch.int32) if num_rows is not None else None),
+         _ptr(out), _stream(data_a))
     return out
 
 
@@ -327,8 +326,7 @@ def _hard_label_raw(prob, gt_label, threshold):
     C = prob.shape[-1]
     N = prob.numel() // C
     out = torch.empty_like(prob)
-    check("pcnn_hard_label_fwd",
-          lib().pcnn_hard_label_fwd(_ptr(prob), _ptr(gt_label), N, C, float(threshold), _ptr(out), _stream(prob)))
+    call("pcnn_hard_label_fwd", _ptr(prob), _ptr(gt_label), N, C, float(threshold), _ptr(out), _stream(prob))
     return out
 
 
@@ -339,7 +337,7 @@ def hard_label_grad(prob, gt_label):
     N = prob.numel() // C
     gp = torch.empty_like(prob)
     gg = torch.empty(gt_label.shape, dtype=torch.float32, device=prob.device)
-    check("pcnn_hard_label_bwd", lib().pcnn_hard_label_bwd(_ptr(gp), _ptr(gg), N, C, _stream(prob)))
+    call("pcnn_hard_label_bwd", _ptr(gp), _ptr(gg), N, C, _stream(prob))
     return gp, gg
 
 
@@ -378,8 +376,7 @@ def softmax_argmax(score, want_prob=True):
     N = score.numel() // C
     prob = torch.empty_like(score) if want_prob else None
     label = torch.empty(score.shape[:-1], dtype=torch.int32, device=score.device)
-    check("pcnn_softmax_argmax_fwd",
-          lib().pcnn_softmax_argmax_fwd(_ptr(score), N, C, _ptr(prob), _ptr(label), _stream(score)))
+    call("pcnn_softmax_argmax_fwd", _ptr(score), N, C, _ptr(prob), _ptr(label), _stream(score))
     return prob, label
 
 
@@ -390,8 +387,7 @@ def bias_act_(x, bias, relu=True):
     C = x.shape[-1]
     if bias.numel() != C:
         raise ValueError("bias must have one entry per channel")
-    check("pcnn_bias_act_fwd",
-          lib().pcnn_bias_act_fwd(_ptr(x), _ptr(bias), x.numel() // C, C, 1 if relu else 0, _ptr(x), _stream(x)))
+    call("pcnn_bias_act_fwd", _ptr(x), _ptr(bias), x.numel() // C, C, 1 if relu else 0, _ptr(x), _stream(x))
     return x
 
 
@@ -408,8 +404,7 @@ def conv3x3_c3(x, weights, bias, relu=True):
     if tuple(weights.shape) != (3, 3, 3, Cout) or bias.numel() != Cout:
         raise ValueError("weights must be [3,3,3,Cout] (ky,kx,ci,co) and bias [Cout]")
     y = torch.empty((B, H, W, Cout), dtype=torch.float32, device=x.device)
-    check("pcnn_conv3x3_c3_fwd",
-          lib().pcnn_conv3x3_c3_fwd(_ptr(x), _ptr(weights), _ptr(bias), B, H, W, Cout, 1 if relu else 0, _ptr(y), _stream(x)))
+    call("pcnn_conv3x3_c3_fwd", _ptr(x), _ptr(weights), _ptr(bias), B, H, W, Cout, 1 if relu else 0, _ptr(y), _stream(x))
     return y
 
 
@@ -426,9 +421,8 @@ def conv3x3_c3_winograd43(x, weights, bias, relu=True, groups=1):
     if weights.numel() != groups * 27 * Cout or tuple(weights.shape[-4:]) != (3, 3, 3, Cout) or bias.numel() != groups * Cout:
         raise ValueError("weights must be [groups,3,3,3,Cout] (ky,kx,ci,co) and bias [groups,Cout]")
     v = torch.empty((36, B * ((H + 3) // 4) * ((W + 3) // 4), Cout), dtype=torch.float32, device=x.device)
-    check("pcnn_conv3x3_c3_winograd43_fwd",
-          lib().pcnn_conv3x3_c3_winograd43_fwd(_ptr(x), _ptr(weights), _ptr(bias), B, H, W, Cout, int(groups),
-                                               1 if relu else 0, _ptr(v), _stream(x)))
+    call("pcnn_conv3x3_c3_winograd43_fwd", _ptr(x), _ptr(weights), _ptr(bias), B, H, W, Cout, int(groups), 1 if relu else 0,
+         _ptr(v), _stream(x))
     return v
 
 
@@ -466,9 +460,8 @@ def conv3x3_c3_winograd43_raw(color_bgr, depth, weights, bias, relu=True, pixel_
     if weights.numel() != sets * 27 * Cout or tuple(weights.shape[-4:]) != (3, 3, 3, Cout) or bias.numel() != sets * Cout:
         raise ValueError("weights must be [sets,3,3,3,Cout] (ky,kx,ci,co) and bias [sets,Cout]")
     v = torch.empty((36, (nc + nd) * ((H + 3) // 4) * ((W + 3) // 4), Cout), dtype=torch.float32, device=dev)
-    check("pcnn_conv3x3_c3_winograd43_raw_fwd",
-          lib().pcnn_conv3x3_c3_winograd43_raw_fwd(_ptr(c), nc, _ptr(d), nd, means, _ptr(weights), _ptr(bias), H, W, Cout,
-                                                   1 if relu else 0, _ptr(v), _stream(v)))
+    call("pcnn_conv3x3_c3_winograd43_raw_fwd", _ptr(c), nc, _ptr(d), nd, means, _ptr(weights), _ptr(bias), H, W, Cout,
+         1 if relu else 0, _ptr(v), _stream(v))
     return v
 
 
@@ -493,9 +486,8 @@ def conv1_1_conv1_2_fused(x, w1, b1, ut2, b2, relu1=True, relu2=True, groups=1, 
     if w1.numel() != groups * 27 * 64 or b1.numel() != groups * 64 or ut2.numel() != groups * 36 * 64 * 64 or b2.numel() != groups * 64:
         raise ValueError("w1 [groups,3,3,3,64], b1 [groups,64], ut2 [groups,36,64,64], b2 [groups,64]")
     y = torch.empty((B, H // 2, W // 2, 64), dtype=torch.float32, device=x.device)
-    check("pcnn_conv1_1_conv1_2_fused_fwd",
-          lib().pcnn_conv1_1_conv1_2_fused_fwd(_ptr(x), _ptr(w1), _ptr(b1), _ptr(ut2), int(ut2_layout), _ptr(b2), B, H, W, int(groups),
-                                               1 if relu1 else 0, 1 if relu2 else 0, _ptr(y), _stream(x)))
+    call("pcnn_conv1_1_conv1_2_fused_fwd", _ptr(x), _ptr(w1), _ptr(b1), _ptr(ut2), int(ut2_layout), _ptr(b2), B, H, W, int(groups),
+         1 if relu1 else 0, 1 if relu2 else 0, _ptr(y), _stream(x))
     return y
 
 
@@ -508,9 +500,8 @@ def conv1_1_conv1_2_fused_raw(color_bgr, depth, w1, b1, ut2, b2, relu1=True, rel
     if w1.numel() != sets * 27 * 64 or b1.numel() != sets * 64 or ut2.numel() != sets * 36 * 64 * 64 or b2.numel() != sets * 64:
         raise ValueError("w1 [sets,3,3,3,64], b1 [sets,64], ut2 [sets,36,64,64], b2 [sets,64]")
     y = torch.empty((nc + nd, H // 2, W // 2, 64), dtype=torch.float32, device=dev)
-    check("pcnn_conv1_1_conv1_2_fused_raw_fwd",
-          lib().pcnn_conv1_1_conv1_2_fused_raw_fwd(_ptr(c), nc, _ptr(d), nd, means, _ptr(w1), _ptr(b1), _ptr(ut2), int(ut2_layout),
-                                                   _ptr(b2), H, W, 1 if relu1 else 0, 1 if relu2 else 0, _ptr(y), _stream(y)))
+    call("pcnn_conv1_1_conv1_2_fused_raw_fwd", _ptr(c), nc, _ptr(d), nd, means, _ptr(w1), _ptr(b1), _ptr(ut2), int(ut2_layout),
+         _ptr(b2), H, W, 1 if relu1 else 0, 1 if relu2 else 0, _ptr(y), _stream(y))
     return y
 
 
@@ -545,7 +536,7 @@ def winograd_input(x, tile=2):
     n = tile + 2
     v = torch.empty((n * n, _wino_tiles(B, H, W, tile), C), dtype=torch.float32, device=x.device)
     fn = "pcnn_winograd_input_fwd" if tile == 2 else "pcnn_winograd43_input_fwd"
-    check(fn, getattr(lib(), fn)(_ptr(x), B, H, W, C, _ptr(v), _stream(x)))
+    call(fn, _ptr(x), B, H, W, C, _ptr(v), _stream(x))
     return v
 
 
@@ -560,7 +551,7 @@ def winograd_output(m, bias, B, H, W, relu=True, pool=False, tile=2):
     shape = (B, H // 2, W // 2, C) if pool else (B, H, W, C)
     y = torch.empty(shape, dtype=torch.float32, device=m.device)
     fn = "pcnn_winograd_output_fwd" if tile == 2 else "pcnn_winograd43_output_fwd"
-    check(fn, getattr(lib(), fn)(_ptr(m), _ptr(bias), B, H, W, C, 1 if relu else 0, 1 if pool else 0, _ptr(y), _stream(m)))
+    call(fn, _ptr(m), _ptr(bias), B, H, W, C, 1 if relu else 0, 1 if pool else 0, _ptr(y), _stream(m))
     return y
 
 
@@ -573,8 +564,7 @@ def winograd43_output_both(m, bias, B, H, W, relu=True):
         raise ValueError("m must be [36, tiles, C] and bias [C]")
     y = torch.empty((B, H, W, C), dtype=torch.float32, device=m.device)
     yp = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=m.device)
-    check("pcnn_winograd43_output_both_fwd",
-          lib().pcnn_winograd43_output_both_fwd(_ptr(m), _ptr(bias), B, H, W, C, 1 if relu else 0, _ptr(y), _ptr(yp), _stream(m)))
+    call("pcnn_winograd43_output_both_fwd", _ptr(m), _ptr(bias), B, H, W, C, 1 if relu else 0, _ptr(y), _ptr(yp), _stream(m))
     return y, yp
 
 
@@ -588,8 +578,7 @@ def winograd43_pack_filters(ut):
     groups = ut.shape[0] if ut.dim() == 4 else 1
     Cout, Cin = ut.shape[-2], ut.shape[-1]
     utp = torch.empty_like(ut)
-    check("pcnn_winograd43_pack_filters_fwd",
-          lib().pcnn_winograd43_pack_filters_fwd(_ptr(ut), Cin, Cout, int(groups), _ptr(utp), _stream(ut)))
+    call("pcnn_winograd43_pack_filters_fwd", _ptr(ut), Cin, Cout, int(groups), _ptr(utp), _stream(ut))
     return utp
 
 
@@ -612,14 +601,11 @@ def winograd43_conv(v, ut, bias, B, H, W, relu=True, pool=0, groups=1, packed=Fa
     pool = int(pool)
     y = torch.empty((B, H // 2, W // 2, Cout) if pool == 1 else (B, H, W, Cout), dtype=torch.float32, device=v.device)
     yp = torch.empty((B, H // 2, W // 2, Cout), dtype=torch.float32, device=v.device) if pool == 2 else None
-    nbytes = ctypes.c_size_t()
-    check("pcnn_winograd43_conv_workspace_bytes",
-          lib().pcnn_winograd43_conv_workspace_bytes(B, H, W, Cin, Cout, int(groups), ctypes.byref(nbytes)))
-    ws = _ws(v.device, "wino43_conv").get(nbytes.value, v.device) if nbytes.value else None   # Cin-split partials (small launches only)
+    # Cin-split partials (small launches only)
+    ws, nbytes = _workspace(v.device, "wino43_conv", "pcnn_winograd43_conv_workspace_bytes", B, H, W, Cin, Cout, int(groups), at_least=0)
     fn = "pcnn_winograd43_conv_packed_fwd" if packed else "pcnn_winograd43_conv_fwd"
-    check(fn,
-          getattr(lib(), fn)(_ptr(v), _ptr(ut), _ptr(bias), B, H, W, Cin, Cout, int(groups), 1 if relu else 0,
-                             pool, _ptr(y), _ptr(yp), _ptr(ws), nbytes.value, _stream(v)))
+    call(fn, _ptr(v), _ptr(ut), _ptr(bias), B, H, W, Cin, Cout, int(groups), 1 if relu else 0, pool, _ptr(y), _ptr(yp), _ptr(ws),
+         nbytes, _stream(v))
     return (y, yp) if pool == 2 else y
 
 
@@ -639,11 +625,9 @@ def fc_rows(x, wt, bias, relu=True, num_rows=None, addend=None):
     ad = _dev(addend, "addend", torch.float32) if addend is not None else None
     if ad is not None and tuple(ad.shape) != (M, N):
         raise ValueError("addend must be [M, N]")
-    nbytes = ctypes.c_size_t()
-    check("pcnn_fc_rows_workspace_bytes", lib().pcnn_fc_rows_workspace_bytes(M, K, N, ctypes.byref(nbytes)))
-    ws = _ws(x.device, "fc_rows").get(nbytes.value, x.device) if nbytes.value else None   # split-K partials (few live rows)
-    check("pcnn_fc_rows_fwd", lib().pcnn_fc_rows_fwd(_ptr(x), _ptr(wt), _ptr(bias), M, K, N, 1 if relu else 0, _ptr(nr), _ptr(ad), _ptr(y),
-                                                    _ptr(ws), nbytes.value, _stream(x)))
+    ws, nbytes = _workspace(x.device, "fc_rows", "pcnn_fc_rows_workspace_bytes", M, K, N, at_least=0)   # split-K partials (few live rows)
+    call("pcnn_fc_rows_fwd", _ptr(x), _ptr(wt), _ptr(bias), M, K, N, 1 if relu else 0, _ptr(nr), _ptr(ad), _ptr(y), _ptr(ws),
+         nbytes, _stream(x))
     return y
 
 
@@ -660,8 +644,8 @@ def fc_rows_split(x, wt, bias, out_a, relu_a=True, relu_b=False, num_rows=None):
     ya = torch.empty((M, int(out_a)), dtype=torch.float32, device=x.device)
     yb = torch.empty((M, out_b), dtype=torch.float32, device=x.device)
     nr = _dev(num_rows, "num_rows", torch.int32) if num_rows is not None else None
-    check("pcnn_fc_rows_split_fwd", lib().pcnn_fc_rows_split_fwd(_ptr(x), _ptr(wt), _ptr(bias), M, K, int(out_a), out_b, 1 if relu_a else 0,
-                                                                1 if relu_b else 0, _ptr(nr), _ptr(ya), _ptr(yb), _stream(x)))
+    call("pcnn_fc_rows_split_fwd", _ptr(x), _ptr(wt), _ptr(bias), M, K, int(out_a), out_b, 1 if relu_a else 0, 1 if relu_b else 0,
+         _ptr(nr), _ptr(ya), _ptr(yb), _stream(x))
     return ya, yb
 
 
@@ -678,8 +662,8 @@ def fc_rows_cols(x, wt_padded, bias_padded, out_features, activation="none", num
     y = torch.empty((M, int(out_features)), dtype=torch.float32, device=x.device)
     y2 = torch.empty_like(y) if act == 2 else None
     nr = _dev(num_rows, "num_rows", torch.int32) if num_rows is not None else None
-    check("pcnn_fc_rows_cols_fwd", lib().pcnn_fc_rows_cols_fwd(_ptr(x), _ptr(wt_padded), _ptr(bias_padded), M, K, wt_padded.shape[0],
-                                                              int(out_features), act, _ptr(nr), _ptr(y), _ptr(y2), _stream(x)))
+    call("pcnn_fc_rows_cols_fwd", _ptr(x), _ptr(wt_padded), _ptr(bias_padded), M, K, wt_padded.shape[0], int(out_features), act,
+         _ptr(nr), _ptr(y), _ptr(y2), _stream(x))
     return (y, y2) if act == 2 else y
 
 
@@ -720,11 +704,11 @@ def fc_skinny(x, wt, bias, activation="none", num_rows=None):
     y2 = torch.empty((M, N), dtype=torch.float32, device=x.device) if act == 2 else None
     nr = _dev(num_rows, "num_rows", torch.int32) if num_rows is not None else None
     nbytes, ncnt = ctypes.c_size_t(), ctypes.c_int()
-    check("pcnn_fc_skinny_workspace_bytes", lib().pcnn_fc_skinny_workspace_bytes(M, K, N, ctypes.byref(nbytes), ctypes.byref(ncnt)))
+    call("pcnn_fc_skinny_workspace_bytes", M, K, N, ctypes.byref(nbytes), ctypes.byref(ncnt))
     ws = _ws(x.device, "fc_skinny").get(nbytes.value, x.device)
     cnt = _ticket_buffer(x.device, ncnt.value)
-    check("pcnn_fc_skinny_fwd", lib().pcnn_fc_skinny_fwd(_ptr(x), _ptr(wt), _ptr(bias), M, K, N, act, _ptr(nr), _ptr(y), _ptr(y2),
-                                                        _ptr(ws), nbytes.value, _ptr(cnt), cnt.numel(), _stream(x)))
+    call("pcnn_fc_skinny_fwd", _ptr(x), _ptr(wt), _ptr(bias), M, K, N, act, _ptr(nr), _ptr(y), _ptr(y2), _ptr(ws), nbytes.value,
+         _ptr(cnt), cnt.numel(), _stream(x))
     return (y, y2) if act == 2 else y
 
 
@@ -749,8 +733,8 @@ def head_lowres(score4, score5, weights_t, planted=None, kernel=4, stride=2):
         raise ValueError("score4 [B,h,w,U], score5 [B,h/s,w/s,U], weights_t [U,Cout], planted like score4")
     Cout = weights_t.shape[1]
     z = torch.empty((B, h, w, Cout), dtype=torch.float32, device=score4.device)
-    check("pcnn_head_lowres_fwd", lib().pcnn_head_lowres_fwd(_ptr(score4), _ptr(score5), _ptr(pl), _ptr(weights_t), B, h, w, U, Cout,
-                                                            int(kernel), int(stride), _ptr(add), _ptr(z), _stream(score4)))
+    call("pcnn_head_lowres_fwd", _ptr(score4), _ptr(score5), _ptr(pl), _ptr(weights_t), B, h, w, U, Cout, int(kernel), int(stride),
+         _ptr(add), _ptr(z), _stream(score4))
     return add, z
 
 
@@ -772,8 +756,8 @@ def head_lowres_mfma(score4, score5, weights_nk, out_channels, planted=None, ker
     if not fits or tuple(weights_nk.shape) != ((Cout + 15) // 16 * 16, U):
         raise ValueError("score4 [B,h,w,U], score5 [B,h/s,w/s,U], weights_nk [ceil(Cout/16)*16, U], planted like score4")
     z = torch.empty((B, h, w, Cout), dtype=torch.float32, device=score4.device)
-    check("pcnn_head_lowres_mfma_fwd", lib().pcnn_head_lowres_mfma_fwd(_ptr(score4), _ptr(score5), _ptr(pl), _ptr(weights_nk), B, h, w, U, Cout,
-                                                                      int(kernel), int(stride), _ptr(add), _ptr(z), _stream(score4)))
+    call("pcnn_head_lowres_mfma_fwd", _ptr(score4), _ptr(score5), _ptr(pl), _ptr(weights_nk), B, h, w, U, Cout, int(kernel),
+         int(stride), _ptr(add), _ptr(z), _stream(score4))
     return add, z
 
 
@@ -786,7 +770,7 @@ def pose_l2_normalize(poses_tanh, poses_weight, num_rows=None):
         raise ValueError("poses_tanh and poses_weight must be [R, 4C]")
     nr = _dev(num_rows, "num_rows", torch.int32) if num_rows is not None else None
     out = torch.empty_like(x)
-    check("pcnn_pose_l2_normalize_fwd", lib().pcnn_pose_l2_normalize_fwd(_ptr(x), _ptr(w), _ptr(nr), x.shape[0], x.shape[1], _ptr(out), _stream(x)))
+    call("pcnn_pose_l2_normalize_fwd", _ptr(x), _ptr(w), _ptr(nr), x.shape[0], x.shape[1], _ptr(out), _stream(x))
     return out
 
 
@@ -809,13 +793,12 @@ def det_assemble(rois, poses_tanh, top_pose, num_rows, row_stride=1, frame_offse
     count = torch.empty((1,), dtype=torch.int32, device=rois.device)
     if frame_offset is not None:
         block = torch.empty((n_out + 1, 14), dtype=torch.float32, device=rois.device)
-        check("pcnn_det_assemble_packed_fwd",
-              lib().pcnn_det_assemble_packed_fwd(_ptr(rois), _ptr(poses_tanh), _ptr(top_pose), _ptr(nr), R, int(row_stride),
-                                                 poses_tanh.shape[1] // 4, float(frame_offset), _ptr(block), _ptr(count), _stream(rois)))
+        call("pcnn_det_assemble_packed_fwd", _ptr(rois), _ptr(poses_tanh), _ptr(top_pose), _ptr(nr), R, int(row_stride),
+             poses_tanh.shape[1] // 4, float(frame_offset), _ptr(block), _ptr(count), _stream(rois))
         return block[:n_out], count, block
     rows = torch.empty((n_out, 14), dtype=torch.float32, device=rois.device)
-    check("pcnn_det_assemble_fwd", lib().pcnn_det_assemble_fwd(_ptr(rois), _ptr(poses_tanh), _ptr(top_pose), _ptr(nr), R, int(row_stride),
-                                                              poses_tanh.shape[1] // 4, _ptr(rows), _ptr(count), _stream(rois)))
+    call("pcnn_det_assemble_fwd", _ptr(rois), _ptr(poses_tanh), _ptr(top_pose), _ptr(nr), R, int(row_stride),
+         poses_tanh.shape[1] // 4, _ptr(rows), _ptr(count), _stream(rois))
     return rows, count
 
 
@@ -837,8 +820,7 @@ def bias_relu_pool2(x, bias, relu=True):
     if bias.numel() != C:
         raise ValueError("bias must have one entry per channel")
     y = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-    check("pcnn_bias_relu_pool2_fwd",
-          lib().pcnn_bias_relu_pool2_fwd(_ptr(x), _ptr(bias), B, H, W, C, 1 if relu else 0, _ptr(y), _stream(x)))
+    call("pcnn_bias_relu_pool2_fwd", _ptr(x), _ptr(bias), B, H, W, C, 1 if relu else 0, _ptr(y), _stream(x))
     return y
 
 
@@ -854,9 +836,8 @@ def _deconv_bilinear_raw(input, kernel, stride, add1=None, add2=None, bias=None,
     for t in (a1, a2):
         if t is not None and tuple(t.shape) != tuple(out.shape):
             raise ValueError("addend must have the output shape %s" % (tuple(out.shape),))
-    check("pcnn_deconv_bilinear_fwd",
-          lib().pcnn_deconv_bilinear_fwd(_ptr(input), B, H, W, C, int(kernel), int(stride), _ptr(a1), _ptr(a2),
-                                         _ptr(bs), 1 if relu else 0, _ptr(out), _stream(input)))
+    call("pcnn_deconv_bilinear_fwd", _ptr(input), B, H, W, C, int(kernel), int(stride), _ptr(a1), _ptr(a2), _ptr(bs),
+         1 if relu else 0, _ptr(out), _stream(input))
     return out
 
 
@@ -867,9 +848,8 @@ def deconv_bilinear_grad(grad_out, kernel, stride):
     if Ho % stride or Wo % stride:
         raise ValueError("grad_out is not a multiple of the stride")
     gin = torch.empty((B, Ho // stride, Wo // stride, C), dtype=torch.float32, device=grad_out.device)
-    check("pcnn_deconv_bilinear_bwd",
-          lib().pcnn_deconv_bilinear_bwd(_ptr(grad_out), B, Ho // stride, Wo // stride, C, int(kernel), int(stride),
-                                         _ptr(gin), _stream(grad_out)))
+    call("pcnn_deconv_bilinear_bwd", _ptr(grad_out), B, Ho // stride, Wo // stride, C, int(kernel), int(stride), _ptr(gin),
+         _stream(grad_out))
     return gin
 
 
@@ -906,12 +886,9 @@ class _SmoothL1VertexFn(torch.autograd.Function):
     def forward(ctx, pred, target, weight, sigma):
         n = pred.numel()
         out = torch.empty(3, dtype=torch.float32, device=pred.device)
-        nbytes = c_size_t(0)
-        check("pcnn_smooth_l1_vertex_workspace_bytes", lib().pcnn_smooth_l1_vertex_workspace_bytes(ctypes.byref(nbytes)))
-        ws = _ws(pred.device, "smooth_l1").get(nbytes.value, pred.device)
-        check("pcnn_smooth_l1_vertex_fwd",
-              lib().pcnn_smooth_l1_vertex_fwd(_ptr(pred), _ptr(target), _ptr(weight), n, float(sigma), _ptr(out),
-                                              _ptr(ws), ws.numel(), _stream(pred)))
+        ws, _ = _workspace(pred.device, "smooth_l1", "pcnn_smooth_l1_vertex_workspace_bytes")
+        call("pcnn_smooth_l1_vertex_fwd", _ptr(pred), _ptr(target), _ptr(weight), n, float(sigma), _ptr(out), _ptr(ws), ws.numel(),
+             _stream(pred))
         ctx.save_for_backward(pred, target, weight, out)
         ctx.sigma = float(sigma)
         return out[0], out[1:].clone()
@@ -921,9 +898,8 @@ class _SmoothL1VertexFn(torch.autograd.Function):
         pred, target, weight, out = ctx.saved_tensors
         grad = torch.empty_like(pred)
         up = grad_loss.reshape(1).to(torch.float32).contiguous()
-        check("pcnn_smooth_l1_vertex_bwd",
-              lib().pcnn_smooth_l1_vertex_bwd(_ptr(pred), _ptr(target), _ptr(weight), _ptr(out), _ptr(up), pred.numel(),
-                                              ctx.sigma, _ptr(grad), _stream(pred)))
+        call("pcnn_smooth_l1_vertex_bwd", _ptr(pred), _ptr(target), _ptr(weight), _ptr(out), _ptr(up), pred.numel(), ctx.sigma,
+             _ptr(grad), _stream(pred))
         return grad, None, None, None
 
 
@@ -963,9 +939,8 @@ def vertex_targets(gt_label_2d, objects, num_classes, instance=None):
     C = int(num_classes)
     targets = torch.empty((B, H, W, 3 * C), dtype=torch.float32, device=label.device)
     weights = torch.empty((B, H, W, 3 * C), dtype=torch.float32, device=label.device)
-    check("pcnn_vertex_targets_fwd",
-          lib().pcnn_vertex_targets_fwd(_ptr(label), _ptr(instance), _ptr(obj), B, H, W, C, obj.shape[1], _ptr(targets),
-                                        _ptr(weights), _stream(label)))
+    call("pcnn_vertex_targets_fwd", _ptr(label), _ptr(instance), _ptr(obj), B, H, W, C, obj.shape[1], _ptr(targets), _ptr(weights),
+         _stream(label))
     return targets, weights
 
 
@@ -974,12 +949,9 @@ class _SmoothL1VertexGtFn(torch.autograd.Function):
     def forward(ctx, pred, label, instance, obj, sigma):
         B, H, W, C3 = pred.shape
         out = torch.empty(3, dtype=torch.float32, device=pred.device)
-        nbytes = c_size_t(0)
-        check("pcnn_smooth_l1_vertex_workspace_bytes", lib().pcnn_smooth_l1_vertex_workspace_bytes(ctypes.byref(nbytes)))
-        ws = _ws(pred.device, "smooth_l1").get(nbytes.value, pred.device)
-        check("pcnn_smooth_l1_vertex_gt_fwd",
-              lib().pcnn_smooth_l1_vertex_gt_fwd(_ptr(pred), _ptr(label), _ptr(instance), _ptr(obj), B, H, W, C3 // 3,
-                                                 obj.shape[1], float(sigma), _ptr(out), _ptr(ws), ws.numel(), _stream(pred)))
+        ws, _ = _workspace(pred.device, "smooth_l1", "pcnn_smooth_l1_vertex_workspace_bytes")
+        call("pcnn_smooth_l1_vertex_gt_fwd", _ptr(pred), _ptr(label), _ptr(instance), _ptr(obj), B, H, W, C3 // 3, obj.shape[1],
+             float(sigma), _ptr(out), _ptr(ws), ws.numel(), _stream(pred))
         ctx.save_for_backward(pred, label, obj, out, instance)
         ctx.sigma = float(sigma)
         return out[0], out[1:].clone()
@@ -990,9 +962,8 @@ class _SmoothL1VertexGtFn(torch.autograd.Function):
         B, H, W, C3 = pred.shape
         grad = torch.empty_like(pred)
         up = grad_loss.reshape(1).to(torch.float32).contiguous()
-        check("pcnn_smooth_l1_vertex_gt_bwd",
-              lib().pcnn_smooth_l1_vertex_gt_bwd(_ptr(pred), _ptr(label), _ptr(instance), _ptr(obj), _ptr(out), _ptr(up),
-                                                 B, H, W, C3 // 3, obj.shape[1], ctx.sigma, _ptr(grad), _stream(pred)))
+        call("pcnn_smooth_l1_vertex_gt_bwd", _ptr(pred), _ptr(label), _ptr(instance), _ptr(obj), _ptr(out), _ptr(up), B, H, W,
+             C3 // 3, obj.shape[1], ctx.sigma, _ptr(grad), _stream(pred))
         return grad, None, None, None, None
 
 
@@ -1031,14 +1002,11 @@ def upscore_softmax_argmax(z, bias, kernel, stride, relu=True, want_score=False,
         if tuple(gt.shape) != (B, Ho, Wo):
             raise ValueError("hard_gt must be int32 [B, H*stride, W*stride]")
         hard = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=dev)
-        check("pcnn_upscore_softmax_argmax_hard_fwd",
-              lib().pcnn_upscore_softmax_argmax_hard_fwd(_ptr(z), _ptr(bias), B, H, W, C, int(kernel), int(stride),
-                                                         1 if relu else 0, _ptr(score), _ptr(prob), _ptr(label),
-                                                         _ptr(gt), float(hard_threshold), _ptr(hard), _stream(z)))
+        call("pcnn_upscore_softmax_argmax_hard_fwd", _ptr(z), _ptr(bias), B, H, W, C, int(kernel), int(stride), 1 if relu else 0,
+             _ptr(score), _ptr(prob), _ptr(label), _ptr(gt), float(hard_threshold), _ptr(hard), _stream(z))
         return score, prob, label, hard
-    check("pcnn_upscore_softmax_argmax_fwd",
-          lib().pcnn_upscore_softmax_argmax_fwd(_ptr(z), _ptr(bias), B, H, W, C, int(kernel), int(stride),
-                                                1 if relu else 0, _ptr(score), _ptr(prob), _ptr(label), _stream(z)))
+    call("pcnn_upscore_softmax_argmax_fwd", _ptr(z), _ptr(bias), B, H, W, C, int(kernel), int(stride), 1 if relu else 0,
+         _ptr(score), _ptr(prob), _ptr(label), _stream(z))
     return score, prob, label
 
 
@@ -1052,10 +1020,7 @@ def _label_head_loss_args(z, bias, gt_label_2d, kernel, stride):
     if tuple(gt.shape) != (B, H * stride, W * stride):
         raise ValueError("gt_label_2d must be int32 [B, H*stride, W*stride] = %s (got %s)"
                          % ((B, H * stride, W * stride), tuple(gt.shape)))
-    nbytes = c_size_t(0)
-    check("pcnn_label_head_loss_workspace_bytes",
-          lib().pcnn_label_head_loss_workspace_bytes(B, H, W, C, int(kernel), int(stride), ctypes.byref(nbytes)))
-    ws = _ws(z.device, "label_head_loss").get(nbytes.value, z.device)
+    ws, _ = _workspace(z.device, "label_head_loss", "pcnn_label_head_loss_workspace_bytes", B, H, W, C, int(kernel), int(stride))
     return z, bias, gt, ws
 
 
@@ -1069,10 +1034,8 @@ def _label_head_loss_raw(z, bias, gt_label_2d, threshold, kernel, stride, relu=T
     sums = torch.empty(2, dtype=torch.float64, device=dev)
     label = torch.empty(gt.shape, dtype=torch.int32, device=dev)
     terms = torch.empty(gt.shape, dtype=torch.float32, device=dev) if want_terms else None
-    check("pcnn_label_head_loss_fwd",
-          lib().pcnn_label_head_loss_fwd(_ptr(z), _ptr(bias), _ptr(gt), B, H, W, C, int(kernel), int(stride), 1 if relu else 0,
-                                         float(threshold), _ptr(loss), _ptr(sums), _ptr(label), _ptr(terms), _ptr(ws),
-                                         ws.numel(), _stream(z)))
+    call("pcnn_label_head_loss_fwd", _ptr(z), _ptr(bias), _ptr(gt), B, H, W, C, int(kernel), int(stride), 1 if relu else 0,
+         float(threshold), _ptr(loss), _ptr(sums), _ptr(label), _ptr(terms), _ptr(ws), ws.numel(), _stream(z))
     return loss, sums, label, terms
 
 
@@ -1089,10 +1052,8 @@ def label_head_loss_grad(z, bias, gt_label_2d, threshold, kernel, stride, relu=T
     B, H, W, C = z.shape
     dscore = torch.empty(tuple(gt.shape) + (C,), dtype=torch.float32, device=z.device)
     dbias = torch.empty(C, dtype=torch.float32, device=z.device)
-    check("pcnn_label_head_loss_bwd",
-          lib().pcnn_label_head_loss_bwd(_ptr(z), _ptr(bias), _ptr(gt), _ptr(sums), _ptr(up), B, H, W, C, int(kernel),
-                                         int(stride), 1 if relu else 0, float(threshold), _ptr(dscore), _ptr(dbias), _ptr(ws),
-                                         ws.numel(), _stream(z)))
+    call("pcnn_label_head_loss_bwd", _ptr(z), _ptr(bias), _ptr(gt), _ptr(sums), _ptr(up), B, H, W, C, int(kernel), int(stride),
+         1 if relu else 0, float(threshold), _ptr(dscore), _ptr(dbias), _ptr(ws), ws.numel(), _stream(z))
     return dscore, dbias
 
 
@@ -1141,11 +1102,8 @@ def _vertex_head_loss_args(z, bias, gt_label_2d, objects, instance, kernel, stri
     if tuple(label.shape) != (B, H * stride, W * stride):
         raise ValueError("gt_label_2d must be int32 [B, H*stride, W*stride] = %s (got %s)"
                          % ((B, H * stride, W * stride), tuple(label.shape)))
-    nbytes = c_size_t(0)
-    check("pcnn_vertex_head_loss_workspace_bytes",
-          lib().pcnn_vertex_head_loss_workspace_bytes(B, H, W, C3 // VERTEX_CHANNELS, int(kernel), int(stride),
-                                                      ctypes.byref(nbytes)))
-    ws = _ws(z.device, "vertex_head_loss").get(nbytes.value, z.device)
+    ws, _ = _workspace(z.device, "vertex_head_loss", "pcnn_vertex_head_loss_workspace_bytes", B, H, W, C3 // VERTEX_CHANNELS,
+                       int(kernel), int(stride))
     return z, bias, label, obj, instance, ws
 
 
@@ -1154,10 +1112,8 @@ def _vertex_head_loss_raw(z, bias, gt_label_2d, objects, kernel, stride, instanc
     z, bias, label, obj, instance, ws = _vertex_head_loss_args(z, bias, gt_label_2d, objects, instance, kernel, stride)
     B, H, W, C3 = z.shape
     out = torch.empty(3, dtype=torch.float32, device=z.device)
-    check("pcnn_vertex_head_loss_fwd",
-          lib().pcnn_vertex_head_loss_fwd(_ptr(z), _ptr(bias), _ptr(label), _ptr(instance), _ptr(obj), B, H, W,
-                                          C3 // VERTEX_CHANNELS, obj.shape[1], int(kernel), int(stride), float(sigma), _ptr(out),
-                                          _ptr(ws), ws.numel(), _stream(z)))
+    call("pcnn_vertex_head_loss_fwd", _ptr(z), _ptr(bias), _ptr(label), _ptr(instance), _ptr(obj), B, H, W, C3 // VERTEX_CHANNELS,
+         obj.shape[1], int(kernel), int(stride), float(sigma), _ptr(out), _ptr(ws), ws.numel(), _stream(z))
     return out
 
 
@@ -1173,10 +1129,9 @@ def vertex_head_loss_grad(z, bias, gt_label_2d, objects, kernel, stride, instanc
     B, H, W, C3 = z.shape
     dz = torch.empty_like(z)
     dbias = torch.empty(C3, dtype=torch.float32, device=z.device)
-    check("pcnn_vertex_head_loss_bwd",
-          lib().pcnn_vertex_head_loss_bwd(_ptr(z), _ptr(bias), _ptr(label), _ptr(instance), _ptr(obj), _ptr(out), _ptr(up), B, H,
-                                          W, C3 // VERTEX_CHANNELS, obj.shape[1], int(kernel), int(stride), float(sigma),
-                                          _ptr(dz), _ptr(dbias), _ptr(ws), ws.numel(), _stream(z)))
+    call("pcnn_vertex_head_loss_bwd", _ptr(z), _ptr(bias), _ptr(label), _ptr(instance), _ptr(obj), _ptr(out), _ptr(up), B, H, W,
+         C3 // VERTEX_CHANNELS, obj.shape[1], int(kernel), int(stride), float(sigma), _ptr(dz), _ptr(dbias), _ptr(ws), ws.numel(),
+         _stream(z))
     return dz, dbias
 
 
@@ -1218,10 +1173,7 @@ def _channels_first(t):
 def _trunk_dbias_ws(fn_name, shape, device, want):
     if not want:
         return None, None
-    nbytes = c_size_t(0)
-    check(fn_name, getattr(lib(), fn_name)(*(tuple(shape) + (ctypes.byref(nbytes),))))
-    C = shape[-1]
-    return torch.empty(C, dtype=torch.float32, device=device), _ws(device, "trunk_epilogue").get(nbytes.value, device)
+    return torch.empty(shape[-1], dtype=torch.float32, device=device), _workspace(device, "trunk_epilogue", fn_name, *shape)[0]
 
 
 def bias_relu_train_grad(da, a, relu=True, want_dbias=True):
@@ -1238,9 +1190,8 @@ def bias_relu_train_grad(da, a, relu=True, want_dbias=True):
     rows = da.numel() // C
     dy = torch.empty_like(da)
     dbias, ws = _trunk_dbias_ws("pcnn_bias_relu_train_workspace_bytes", (rows, C), da.device, want_dbias)
-    check("pcnn_bias_relu_train_bwd",
-          lib().pcnn_bias_relu_train_bwd(_ptr(da), _ptr(a if relu else None), rows, C, 1 if relu else 0, _ptr(dy), _ptr(dbias),
-                                         _ptr(ws), ws.numel() if ws is not None else 0, _stream(da)))
+    call("pcnn_bias_relu_train_bwd", _ptr(da), _ptr(a if relu else None), rows, C, 1 if relu else 0, _ptr(dy), _ptr(dbias),
+         _ptr(ws), ws.numel() if ws is not None else 0, _stream(da))
     return dy, dbias
 
 
@@ -1296,9 +1247,8 @@ def _bias_relu_pool2_train_raw(y, bias, relu=True, want_act=False):
     pooled = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=y.device)
     sel = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8, device=y.device)
     act = y if want_act else None
-    check("pcnn_bias_relu_pool2_train_fwd",
-          lib().pcnn_bias_relu_pool2_train_fwd(_ptr(y), _ptr(bias), B, H, W, C, 1 if relu else 0, _ptr(act), _ptr(pooled),
-                                               _ptr(sel), _stream(y)))
+    call("pcnn_bias_relu_pool2_train_fwd", _ptr(y), _ptr(bias), B, H, W, C, 1 if relu else 0, _ptr(act), _ptr(pooled), _ptr(sel),
+         _stream(y))
     return act, pooled, sel
 
 
@@ -1320,9 +1270,8 @@ def bias_relu_pool2_train_grad(dpooled, sel, dact=None, act=None, want_dbias=Tru
             raise ValueError("dact and act must be %s (got %s, %s)" % ((B, H, W, C), tuple(dact.shape), tuple(act.shape)))
     dy = torch.empty((B, H, W, C), dtype=torch.float32, device=dpooled.device)
     dbias, ws = _trunk_dbias_ws("pcnn_bias_relu_pool2_train_workspace_bytes", (B, H, W, C), dpooled.device, want_dbias)
-    check("pcnn_bias_relu_pool2_train_bwd",
-          lib().pcnn_bias_relu_pool2_train_bwd(_ptr(dpooled), _ptr(sel), _ptr(dact), _ptr(act), B, H, W, C, _ptr(dy), _ptr(dbias),
-                                               _ptr(ws), ws.numel() if ws is not None else 0, _stream(dpooled)))
+    call("pcnn_bias_relu_pool2_train_bwd", _ptr(dpooled), _ptr(sel), _ptr(dact), _ptr(act), B, H, W, C, _ptr(dy), _ptr(dbias),
+         _ptr(ws), ws.numel() if ws is not None else 0, _stream(dpooled))
     return dy, dbias
 
 
@@ -1386,14 +1335,9 @@ class _AverageDistanceFn(torch.autograd.Function):
         dev = prediction.device
         loss = torch.empty((1,), dtype=torch.float32, device=dev)
         bottom_diff = torch.empty((R, CH), dtype=torch.float32, device=dev)
-        nbytes = c_size_t(0)
-        check("pcnn_average_distance_workspace_bytes",
-              lib().pcnn_average_distance_workspace_bytes(R, C, P, ctypes.byref(nbytes)))
-        ws = _ws(dev, "adl").get(nbytes.value, dev)
-        check("pcnn_average_distance_fwd",
-              lib().pcnn_average_distance_fwd(_ptr(prediction), _ptr(target), _ptr(weight), _ptr(point),
-                                              _ptr(symmetry), R, C, P, float(margin), _ptr(num_rows), _ptr(loss),
-                                              _ptr(bottom_diff), _ptr(ws), ws.numel(), _stream(prediction)))
+        ws, _ = _workspace(dev, "adl", "pcnn_average_distance_workspace_bytes", R, C, P)
+        call("pcnn_average_distance_fwd", _ptr(prediction), _ptr(target), _ptr(weight), _ptr(point), _ptr(symmetry), R, C, P,
+             float(margin), _ptr(num_rows), _ptr(loss), _ptr(bottom_diff), _ptr(ws), ws.numel(), _stream(prediction))
         ctx.save_for_backward(bottom_diff)
         ctx.mark_non_differentiable(bottom_diff)
         return loss, bottom_diff
@@ -1405,9 +1349,7 @@ class _AverageDistanceFn(torch.autograd.Function):
         grad_loss = grad_loss.contiguous()
         out = torch.empty_like(bottom_diff)
         if R > 0:
-            check("pcnn_average_distance_bwd",
-                  lib().pcnn_average_distance_bwd(_ptr(grad_loss), _ptr(bottom_diff), R, CH, _ptr(out),
-                                                  _stream(bottom_diff)))
+            call("pcnn_average_distance_bwd", _ptr(grad_loss), _ptr(bottom_diff), R, CH, _ptr(out), _stream(bottom_diff))
         return out, None, None, None, None, None, None
 
 
@@ -1447,14 +1389,10 @@ class _BackprojectFn(torch.autograd.Function):
         top_flag = torch.empty((B, G, G, G, Cd), dtype=torch.float32, device=dev)
         top_label = torch.empty((B, G, G, G, Cl), dtype=torch.float32, device=dev)
         # caller-owned scratch for the window-range table that lets 85 % of the voxels skip their depth scan
-        need = c_size_t(0)
-        check("pcnn_backproject_workspace_bytes", lib().pcnn_backproject_workspace_bytes(B, H, W, int(kernel_size), ctypes.byref(need)))
-        ws = _ws(dev, "backproject").get(need.value, dev) if need.value else None
-        check("pcnn_backproject_ws_fwd",
-              lib().pcnn_backproject_ws_fwd(_ptr(data), _ptr(label), _ptr(depth), _ptr(meta_data), _ptr(label_3d),
-                                            B, H, W, Cd, Cl, num_meta, G, int(kernel_size), float(threshold),
-                                            _ptr(top_data), _ptr(top_label), _ptr(top_flag),
-                                            _ptr(ws), c_size_t(need.value if ws is not None else 0), _stream(data)))
+        ws, need = _workspace(dev, "backproject", "pcnn_backproject_workspace_bytes", B, H, W, int(kernel_size), at_least=0)
+        call("pcnn_backproject_ws_fwd", _ptr(data), _ptr(label), _ptr(depth), _ptr(meta_data), _ptr(label_3d), B, H, W, Cd, Cl,
+             num_meta, G, int(kernel_size), float(threshold), _ptr(top_data), _ptr(top_label), _ptr(top_flag), _ptr(ws), need,
+             _stream(data))
         ctx.save_for_backward(depth, meta_data)
         ctx.cfg = (B, H, W, Cd, num_meta, G)
         ctx.mark_non_differentiable(top_label, top_flag)
@@ -1466,9 +1404,8 @@ class _BackprojectFn(torch.autograd.Function):
         B, H, W, Cd, num_meta, G = ctx.cfg
         grad_data = grad_data.contiguous()
         bottom = torch.empty((B, H, W, Cd), dtype=torch.float32, device=grad_data.device)
-        check("pcnn_backproject_bwd",
-              lib().pcnn_backproject_bwd(_ptr(grad_data), _ptr(depth), _ptr(meta_data), B, H, W, Cd, num_meta, G,
-                                         _ptr(bottom), _stream(grad_data)))
+        call("pcnn_backproject_bwd", _ptr(grad_data), _ptr(depth), _ptr(meta_data), B, H, W, Cd, num_meta, G, _ptr(bottom),
+             _stream(grad_data))
         return bottom, None, None, None, None, None, None, None
 
 
@@ -1560,9 +1497,8 @@ def depth_normals(depth, intrinsics, depth_cutoff=20.0, factor_depth=None):
     intrinsics f32 [B,4] rows (fx, fy, cx, cy). Returns nmap f32 [B,H,W,3]; NaN (0x7fffffff) where the reference's is."""
     f32, u16, factor, intr, B, H, W = _depth_args(depth, intrinsics, factor_depth)
     nmap = torch.empty((B, H, W, 3), dtype=torch.float32, device=intr.device)
-    check("pcnn_depth_normals_fwd",
-          lib().pcnn_depth_normals_fwd(_ptr(f32), _ptr(u16), factor, _ptr(intr), B, H, W, float(depth_cutoff), _ptr(nmap),
-                                       _stream(nmap)))
+    call("pcnn_depth_normals_fwd", _ptr(f32), _ptr(u16), factor, _ptr(intr), B, H, W, float(depth_cutoff), _ptr(nmap),
+         _stream(nmap))
     return nmap
 
 
@@ -1575,9 +1511,7 @@ def bilateral_filter_u8(image, d=9, sigma_color=75.0, sigma_space=75.0):
     color, space, _ = bilateral_tables(d, sigma_color, sigma_space, image.device)
     B, H, W, _ = image.shape
     out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=image.device)
-    check("pcnn_bilateral_u8c3_fwd",
-          lib().pcnn_bilateral_u8c3_fwd(_ptr(image), B, H, W, int(d), _ptr(color), _ptr(space), space.numel(), _ptr(out),
-                                        _stream(out)))
+    call("pcnn_bilateral_u8c3_fwd", _ptr(image), B, H, W, int(d), _ptr(color), _ptr(space), space.numel(), _ptr(out), _stream(out))
     return out
 
 
@@ -1592,9 +1526,8 @@ def normal_image(depth, intrinsics, factor_depth=None, depth_cutoff=20.0, d=9, s
         color, space, _ = bilateral_tables(d, sigma_color, sigma_space, intr.device)
         taps = space.numel()
     out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=intr.device)
-    check("pcnn_normal_image_fwd",
-          lib().pcnn_normal_image_fwd(_ptr(f32), _ptr(u16), factor, _ptr(intr), B, H, W, float(depth_cutoff), int(d),
-                                      _ptr(color), _ptr(space), taps, _ptr(out), _stream(out)))
+    call("pcnn_normal_image_fwd", _ptr(f32), _ptr(u16), factor, _ptr(intr), B, H, W, float(depth_cutoff), int(d), _ptr(color),
+         _ptr(space), taps, _ptr(out), _stream(out))
     return out
 
 
@@ -1639,14 +1572,10 @@ def augment_frames(color, depth=None, params=None, seed=0, pixel_means=None, dep
     data = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
     data_p = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev) if depth is not None else None
     norm = DEPTH_NORMS[depth_norm]
-    nbytes = c_size_t()
-    check("pcnn_augment_frames_workspace_bytes",
-          lib().pcnn_augment_frames_workspace_bytes(B, 1 if depth is not None else 0, norm, ctypes.byref(nbytes)))
-    ws = _ws(dev, "augment_frames").get(nbytes.value, dev) if nbytes.value else None
-    check("pcnn_augment_frames_fwd",
-          lib().pcnn_augment_frames_fwd(_ptr(color), C, _ptr(depth), ctypes.c_void_p(rows.ctypes.data), means,
-                                        seed & (1 << 64) - 1, seed >> 64, norm, B, H, W, _ptr(data), _ptr(data_p), _ptr(ws),
-                                        nbytes.value, _stream(data)))
+    ws, nbytes = _workspace(dev, "augment_frames", "pcnn_augment_frames_workspace_bytes", B, 1 if depth is not None else 0, norm,
+                            at_least=0)
+    call("pcnn_augment_frames_fwd", _ptr(color), C, _ptr(depth), ctypes.c_void_p(rows.ctypes.data), means, seed & (1 << 64) - 1,
+         seed >> 64, norm, B, H, W, _ptr(data), _ptr(data_p), _ptr(ws), nbytes, _stream(data))
     return data, data_p
 
 
@@ -1656,25 +1585,34 @@ POSE3D_DEFAULTS = dict(hypotheses=256, pixel_batch=1000, max_pixels=1000, ref_it
                        min_dist=0.01, min_pixels=10, max_attempts=1024)   # synthesize.cpp:1783-1799; max_attempts is ours
 
 
-def _pose3d_frames(label_2d, depth, vertex_pred, extents, intrinsics):
+POSE2D_DEFAULTS = dict(hypotheses=256, pixel_batch=1000, max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=10.0,
+                       min_dist2d=10.0, min_dist3d=0.01, min_pixels=10, max_attempts=1024)   # synthesize.cpp:1590-1599; max_attempts is ours
+
+
+# ---- what the two routes' wrappers check and allocate alike
+def _pose_frames(label_2d, vertex_pred, extents, intrinsics=None, depth=None):
+    """The checked frames of both routes; `depth` (uint16 [B,H,W] or [B,H,W,1]) only on the route that has one, `intrinsics`
+    wherever the entry takes them. -> (label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C)."""
     label_2d = _dev(label_2d, "label_2d", torch.int32)
-    depth = _dev(depth, "depth", torch.uint16)
-    if depth.dim() == 4 and depth.shape[3] == 1:
-        depth = depth.reshape(depth.shape[:3])
+    if depth is not None:
+        depth = _dev(depth, "depth", torch.uint16)
+        if depth.dim() == 4 and depth.shape[3] == 1:
+            depth = depth.reshape(depth.shape[:3])
     vertex_pred = _dev(vertex_pred, "vertex_pred", torch.float32)
     extents = _dev(extents, "extents", torch.float32)
-    intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+    if intrinsics is not None:
+        intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
     if label_2d.dim() != 3:
         raise ValueError("label_2d must be [B,H,W] (got %s)" % (tuple(label_2d.shape),))
     B, H, W = label_2d.shape
-    if tuple(depth.shape) != (B, H, W):
+    if depth is not None and tuple(depth.shape) != (B, H, W):
         raise ValueError("depth must be uint16 [%d,%d,%d] (got %s)" % (B, H, W, tuple(depth.shape)))
     if extents.dim() != 2 or extents.shape[1] != 3:
         raise ValueError("extents must be [C,3] (got %s)" % (tuple(extents.shape),))
     C = extents.shape[0]
     if tuple(vertex_pred.shape) != (B, H, W, 3 * C):
         raise ValueError("vertex_pred must be [%d,%d,%d,%d] (got %s)" % (B, H, W, 3 * C, tuple(vertex_pred.shape)))
-    if tuple(intrinsics.shape) != (B, 4):
+    if intrinsics is not None and tuple(intrinsics.shape) != (B, 4):
         raise ValueError("intrinsics must be [B,4] rows (fx, fy, px, py) with B = %d (got %s)" % (B, tuple(intrinsics.shape)))
     return label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C
 
@@ -1700,20 +1638,10 @@ def _pose3d_seed(seed):
     return seed & (1 << 64) - 1, seed >> 64
 
 
-def pose3d_prepare(label_2d, depth, vertex_pred, extents, intrinsics, factor_depth):
-    """The correspondence records of `estimate_poses_3d` (getEye, getLabels, getMode3D): -> (records f32 [B,H*W,6] rows
-    (eye xyz, obj xyz), compacted per (frame, class) in raster order, counts int32 [B,C], offsets int32 [B,C]). Rows past a
-    frame's total are not written."""
-    label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C = _pose3d_frames(label_2d, depth, vertex_pred, extents, intrinsics)
-    dev = label_2d.device
-    records = torch.empty((B, H * W, 6), dtype=torch.float32, device=dev)
-    counts = torch.empty((B, C), dtype=torch.int32, device=dev)
-    offsets = torch.empty((B, C), dtype=torch.int32, device=dev)
-    check("pcnn_pose3d_prepare_fwd",
-          lib().pcnn_pose3d_prepare_fwd(_ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics),
-                                        float(factor_depth), B, H, W, C, _ptr(records), _ptr(counts), _ptr(offsets),
-                                        _stream(records)))
-    return records, counts, offsets
+def _pose_record_outputs(B, H, W, C, dev):
+    """(records f32 [B,H*W,6], counts int32 [B,C], offsets int32 [B,C]) for a prepare entry to fill."""
+    return (torch.empty((B, H * W, 6), dtype=torch.float32, device=dev), torch.empty((B, C), dtype=torch.int32, device=dev),
+            torch.empty((B, C), dtype=torch.int32, device=dev))
 
 
 def _pose3d_records(records, counts, offsets, H, W):
@@ -1728,11 +1656,9 @@ def _pose3d_records(records, counts, offsets, H, W):
     return records, counts, offsets, B, counts.shape[1]
 
 
-def pose3d_sample(records, counts, offsets, extents, intrinsics, height, width, seed=0, streams=None, hypotheses=256,
-                  max_attempts=1024, min_area=400, inlier_threshold=0.01, min_dist=0.01):
-    """One 3-point hypothesis per (frame, h) from `pose3d_prepare`'s records: -> (hyp_pose f64 [B,hypotheses,3,4],
-    hyp_class int32 [B,hypotheses] (0: none found), hyp_attempt int32 (the accepted attempt, -1), hyp_rec int32 [..,3]
-    (the three records, indices inside their class))."""
+def _pose_sample_args(records, counts, offsets, extents, intrinsics, height, width, seed, streams, hypotheses, points):
+    """Everything a sample entry takes in front of its thresholds, checked, and its four outputs, hyp_rec [B,n,points]:
+    -> (the nine pointer / key arguments in the entry's order, (B, H, W, C, n), outputs)."""
     H, W = int(height), int(width)
     records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
     extents = _dev(extents, "extents", torch.float32)
@@ -1743,16 +1669,57 @@ def pose3d_sample(records, counts, offsets, extents, intrinsics, height, width, 
     streams = _pose3d_streams(streams, B, dev)
     s0, s1 = _pose3d_seed(seed)
     n = int(hypotheses)
-    hyp_pose = torch.empty((B, max(n, 0), 3, 4), dtype=torch.float64, device=dev)
-    hyp_class = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
-    hyp_attempt = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
-    hyp_rec = torch.empty((B, max(n, 0), 3), dtype=torch.int32, device=dev)
-    check("pcnn_pose3d_sample_fwd",
-          lib().pcnn_pose3d_sample_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(extents), _ptr(intrinsics), _ptr(streams),
-                                       s0, s1, B, H, W, C, n, int(max_attempts), int(min_area), float(inlier_threshold),
-                                       float(min_dist), _ptr(hyp_pose), _ptr(hyp_class), _ptr(hyp_attempt), _ptr(hyp_rec),
-                                       _stream(records)))
-    return hyp_pose, hyp_class, hyp_attempt, hyp_rec
+    outs = (torch.empty((B, max(n, 0), 3, 4), dtype=torch.float64, device=dev),
+            torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev),
+            torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev),
+            torch.empty((B, max(n, 0), points), dtype=torch.int32, device=dev))
+    return (_ptr(records), _ptr(counts), _ptr(offsets), _ptr(extents), _ptr(intrinsics), _ptr(streams), s0, s1), (B, H, W, C, n), outs
+
+
+def _pose_round_outputs(hyp_pose, hyp_class, B):
+    """The hypothesis-shape check of a round entry and its outputs: -> (n, (pose_out, class_out, inliers_out))."""
+    if hyp_class.dim() != 2 or hyp_class.shape[0] != B or tuple(hyp_pose.shape) != tuple(hyp_class.shape) + (3, 4):
+        raise ValueError("hyp_class must be [B,n] and hyp_pose [B,n,3,4] (got %s, %s)" % (tuple(hyp_class.shape), tuple(hyp_pose.shape)))
+    n, dev = hyp_class.shape[1], hyp_pose.device
+    return n, (torch.empty((B, n, 3, 4), dtype=torch.float64, device=dev), torch.empty((B, n), dtype=torch.int32, device=dev),
+               torch.empty((B, n), dtype=torch.int32, device=dev))
+
+
+def _pose_estimate_args(route, dims, dev, seed, streams, hypotheses, min_pixels, workspace):
+    """What an estimate entry takes besides its frames and thresholds, `route` "pose3d" | "pose2d", dims = (B, H, W, C):
+    -> (streams, s0, s1, workspace buffer, its bytes, (poses64, poses, inliers, ref_steps, num_hyps))."""
+    B, H, W, C = dims
+    streams = _pose3d_streams(streams, B, dev)
+    s0, s1 = _pose3d_seed(seed)
+    int(min_pixels)
+    ws, nbytes = _workspace(dev, route, "pcnn_%s_workspace_bytes" % route, B, H, W, C, int(hypotheses), workspace=workspace)
+    outs = (torch.empty((B, C, 3, 4), dtype=torch.float64, device=dev), torch.empty((B, C, 3, 4), dtype=torch.float32, device=dev),
+            torch.empty((B, C), dtype=torch.int32, device=dev), torch.empty((B, C), dtype=torch.int32, device=dev),
+            torch.empty((B, C), dtype=torch.int32, device=dev))
+    return streams, s0, s1, ws, nbytes, outs
+
+
+# ---- the route with a depth frame
+def pose3d_prepare(label_2d, depth, vertex_pred, extents, intrinsics, factor_depth):
+    """The correspondence records of `estimate_poses_3d` (getEye, getLabels, getMode3D): -> (records f32 [B,H*W,6] rows
+    (eye xyz, obj xyz), compacted per (frame, class) in raster order, counts int32 [B,C], offsets int32 [B,C]). Rows past a
+    frame's total are not written."""
+    label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C = _pose_frames(label_2d, vertex_pred, extents, intrinsics, depth)
+    records, counts, offsets = _pose_record_outputs(B, H, W, C, label_2d.device)
+    call("pcnn_pose3d_prepare_fwd", _ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics),
+         float(factor_depth), B, H, W, C, _ptr(records), _ptr(counts), _ptr(offsets), _stream(records))
+    return records, counts, offsets
+
+
+def pose3d_sample(records, counts, offsets, extents, intrinsics, height, width, seed=0, streams=None, hypotheses=256,
+                  max_attempts=1024, min_area=400, inlier_threshold=0.01, min_dist=0.01):
+    """One 3-point hypothesis per (frame, h) from `pose3d_prepare`'s records: -> (hyp_pose f64 [B,hypotheses,3,4],
+    hyp_class int32 [B,hypotheses] (0: none found), hyp_attempt int32 (the accepted attempt, -1), hyp_rec int32 [..,3]
+    (the three records, indices inside their class))."""
+    args, dims, outs = _pose_sample_args(records, counts, offsets, extents, intrinsics, height, width, seed, streams, hypotheses, 3)
+    call("pcnn_pose3d_sample_fwd", *args, *dims, int(max_attempts), int(min_area), float(inlier_threshold), float(min_dist),
+         *map(_ptr, outs), _stream(outs[0]))
+    return outs
 
 
 def pose3d_round(records, counts, offsets, hyp_pose, hyp_class, height, width, round, pixel_batch=1000, max_pixels=1000,
@@ -1763,18 +1730,10 @@ def pose3d_round(records, counts, offsets, hyp_pose, hyp_class, height, width, r
     records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
     hyp_pose = _dev(hyp_pose, "hyp_pose", torch.float64)
     hyp_class = _dev(hyp_class, "hyp_class", torch.int32)
-    if hyp_class.dim() != 2 or hyp_class.shape[0] != B or tuple(hyp_pose.shape) != tuple(hyp_class.shape) + (3, 4):
-        raise ValueError("hyp_class must be [B,n] and hyp_pose [B,n,3,4] (got %s, %s)" % (tuple(hyp_class.shape), tuple(hyp_pose.shape)))
-    n = hyp_class.shape[1]
-    dev = records.device
-    pose_out = torch.empty((B, n, 3, 4), dtype=torch.float64, device=dev)
-    class_out = torch.empty((B, n), dtype=torch.int32, device=dev)
-    inliers_out = torch.empty((B, n), dtype=torch.int32, device=dev)
-    check("pcnn_pose3d_round_fwd",
-          lib().pcnn_pose3d_round_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(hyp_pose), _ptr(hyp_class), B, H, W, C, n,
-                                      int(round), int(pixel_batch), int(max_pixels), float(inlier_threshold), _ptr(pose_out),
-                                      _ptr(class_out), _ptr(inliers_out), _stream(records)))
-    return pose_out, class_out, inliers_out
+    n, outs = _pose_round_outputs(hyp_pose, hyp_class, B)
+    call("pcnn_pose3d_round_fwd", _ptr(records), _ptr(counts), _ptr(offsets), _ptr(hyp_pose), _ptr(hyp_class), B, H, W, C, n,
+         int(round), int(pixel_batch), int(max_pixels), float(inlier_threshold), *map(_ptr, outs), _stream(records))
+    return outs
 
 
 def estimate_poses_3d(label_2d, depth, vertex_pred, extents, intrinsics, factor_depth, seed=0, streams=None, hypotheses=256,
@@ -1788,65 +1747,25 @@ def estimate_poses_3d(label_2d, depth, vertex_pred, extents, intrinsics, factor_
     Returns device tensors (poses f32 [B,C,3,4], poses64 f64 [B,C,3,4], inliers, ref_steps, num_hyps int32 [B,C]); a class
     without hypothesis is all zero (the reference's caller reads t_z > 0 as found). Deviations from the reference:
     DESIGN.md 3.7b."""
-    label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C = _pose3d_frames(label_2d, depth, vertex_pred, extents, intrinsics)
-    dev = label_2d.device
-    streams = _pose3d_streams(streams, B, dev)
-    s0, s1 = _pose3d_seed(seed)
-    int(min_pixels)
-    nbytes = c_size_t()
-    check("pcnn_pose3d_workspace_bytes", lib().pcnn_pose3d_workspace_bytes(B, H, W, C, int(hypotheses), ctypes.byref(nbytes)))
-    ws = (workspace or _ws(dev, "pose3d")).get(nbytes.value, dev)
-    poses64 = torch.empty((B, C, 3, 4), dtype=torch.float64, device=dev)
-    poses = torch.empty((B, C, 3, 4), dtype=torch.float32, device=dev)
-    inliers = torch.empty((B, C), dtype=torch.int32, device=dev)
-    ref_steps = torch.empty((B, C), dtype=torch.int32, device=dev)
-    num_hyps = torch.empty((B, C), dtype=torch.int32, device=dev)
-    check("pcnn_pose3d_estimate_fwd",
-          lib().pcnn_pose3d_estimate_fwd(_ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics),
-                                         _ptr(streams), float(factor_depth), s0, s1, B, H, W, C, int(hypotheses), int(pixel_batch),
-                                         int(max_pixels), int(ref_it), int(min_area), float(inlier_threshold), float(min_dist),
-                                         int(max_attempts), _ptr(poses64), _ptr(poses), _ptr(inliers), _ptr(ref_steps),
-                                         _ptr(num_hyps), _ptr(ws), nbytes.value, _stream(poses)))
+    label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C = _pose_frames(label_2d, vertex_pred, extents, intrinsics, depth)
+    streams, s0, s1, ws, nbytes, outs = _pose_estimate_args("pose3d", (B, H, W, C), label_2d.device, seed, streams, hypotheses,
+                                                            min_pixels, workspace)
+    call("pcnn_pose3d_estimate_fwd", _ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics), _ptr(streams),
+         float(factor_depth), s0, s1, B, H, W, C, int(hypotheses), int(pixel_batch), int(max_pixels), int(ref_it), int(min_area),
+         float(inlier_threshold), float(min_dist), int(max_attempts), *map(_ptr, outs), _ptr(ws), nbytes, _stream(outs[1]))
+    poses64, poses, inliers, ref_steps, num_hyps = outs
     return poses, poses64, inliers, ref_steps, num_hyps
 
 
-# ------------------------------------------------------------------------------------------------
-# 3-D vertex route without depth: preemptive RANSAC with P3P hypotheses and a Gauss-Newton refit (include/posecnn_hip_pose2d.h)
-POSE2D_DEFAULTS = dict(hypotheses=256, pixel_batch=1000, max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=10.0,
-                       min_dist2d=10.0, min_dist3d=0.01, min_pixels=10, max_attempts=1024)   # synthesize.cpp:1590-1599; max_attempts is ours
-
-
-def _pose2d_frames(label_2d, vertex_pred, extents, intrinsics=None):
-    label_2d = _dev(label_2d, "label_2d", torch.int32)
-    vertex_pred = _dev(vertex_pred, "vertex_pred", torch.float32)
-    extents = _dev(extents, "extents", torch.float32)
-    if label_2d.dim() != 3:
-        raise ValueError("label_2d must be [B,H,W] (got %s)" % (tuple(label_2d.shape),))
-    B, H, W = label_2d.shape
-    if extents.dim() != 2 or extents.shape[1] != 3:
-        raise ValueError("extents must be [C,3] (got %s)" % (tuple(extents.shape),))
-    C = extents.shape[0]
-    if tuple(vertex_pred.shape) != (B, H, W, 3 * C):
-        raise ValueError("vertex_pred must be [%d,%d,%d,%d] (got %s)" % (B, H, W, 3 * C, tuple(vertex_pred.shape)))
-    if intrinsics is not None:
-        intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
-        if tuple(intrinsics.shape) != (B, 4):
-            raise ValueError("intrinsics must be [B,4] rows (fx, fy, px, py) with B = %d (got %s)" % (B, tuple(intrinsics.shape)))
-    return label_2d, vertex_pred, extents, intrinsics, B, H, W, C
-
-
+# ---- the route without depth: P3P hypotheses and a Gauss-Newton refit (include/posecnn_hip_pose2d.h)
 def pose2d_prepare(label_2d, vertex_pred, extents):
     """The correspondence records of `estimate_poses_2d`: -> (records f32 [B,H*W,6] rows (pixel x, pixel y, 0, obj xyz),
     compacted per (frame, class) in raster order, counts int32 [B,C], offsets int32 [B,C]). Rows past a frame's total are
     not written."""
-    label_2d, vertex_pred, extents, _, B, H, W, C = _pose2d_frames(label_2d, vertex_pred, extents)
-    dev = label_2d.device
-    records = torch.empty((B, H * W, 6), dtype=torch.float32, device=dev)
-    counts = torch.empty((B, C), dtype=torch.int32, device=dev)
-    offsets = torch.empty((B, C), dtype=torch.int32, device=dev)
-    check("pcnn_pose2d_prepare_fwd",
-          lib().pcnn_pose2d_prepare_fwd(_ptr(label_2d), _ptr(vertex_pred), _ptr(extents), B, H, W, C, _ptr(records), _ptr(counts),
-                                        _ptr(offsets), _stream(records)))
+    label_2d, _, vertex_pred, extents, _, B, H, W, C = _pose_frames(label_2d, vertex_pred, extents)
+    records, counts, offsets = _pose_record_outputs(B, H, W, C, label_2d.device)
+    call("pcnn_pose2d_prepare_fwd", _ptr(label_2d), _ptr(vertex_pred), _ptr(extents), B, H, W, C, _ptr(records), _ptr(counts),
+         _ptr(offsets), _stream(records))
     return records, counts, offsets
 
 
@@ -1855,26 +1774,10 @@ def pose2d_sample(records, counts, offsets, extents, intrinsics, height, width, 
     """One 4-point hypothesis per (frame, h) from `pose2d_prepare`'s records — P3P on three pairs, the fourth chooses the
     root: -> (hyp_pose f64 [B,hypotheses,3,4], hyp_class int32 [B,hypotheses] (0: none found), hyp_attempt int32 (the
     accepted attempt, -1), hyp_rec int32 [..,4] (the four records, indices inside their class))."""
-    H, W = int(height), int(width)
-    records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
-    extents = _dev(extents, "extents", torch.float32)
-    intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
-    if tuple(extents.shape) != (C, 3) or tuple(intrinsics.shape) != (B, 4):
-        raise ValueError("extents must be [%d,3] and intrinsics [%d,4]" % (C, B))
-    dev = records.device
-    streams = _pose3d_streams(streams, B, dev)
-    s0, s1 = _pose3d_seed(seed)
-    n = int(hypotheses)
-    hyp_pose = torch.empty((B, max(n, 0), 3, 4), dtype=torch.float64, device=dev)
-    hyp_class = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
-    hyp_attempt = torch.empty((B, max(n, 0)), dtype=torch.int32, device=dev)
-    hyp_rec = torch.empty((B, max(n, 0), 4), dtype=torch.int32, device=dev)
-    check("pcnn_pose2d_sample_fwd",
-          lib().pcnn_pose2d_sample_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(extents), _ptr(intrinsics), _ptr(streams),
-                                       s0, s1, B, H, W, C, n, int(max_attempts), int(min_area), float(inlier_threshold),
-                                       float(min_dist2d), float(min_dist3d), _ptr(hyp_pose), _ptr(hyp_class), _ptr(hyp_attempt),
-                                       _ptr(hyp_rec), _stream(records)))
-    return hyp_pose, hyp_class, hyp_attempt, hyp_rec
+    args, dims, outs = _pose_sample_args(records, counts, offsets, extents, intrinsics, height, width, seed, streams, hypotheses, 4)
+    call("pcnn_pose2d_sample_fwd", *args, *dims, int(max_attempts), int(min_area), float(inlier_threshold), float(min_dist2d),
+         float(min_dist3d), *map(_ptr, outs), _stream(outs[0]))
+    return outs
 
 
 def pose2d_round(records, counts, offsets, intrinsics, hyp_pose, hyp_class, height, width, round, pixel_batch=1000,
@@ -1888,18 +1791,10 @@ def pose2d_round(records, counts, offsets, intrinsics, hyp_pose, hyp_class, heig
     hyp_class = _dev(hyp_class, "hyp_class", torch.int32)
     if tuple(intrinsics.shape) != (B, 4):
         raise ValueError("intrinsics must be [%d,4] (got %s)" % (B, tuple(intrinsics.shape)))
-    if hyp_class.dim() != 2 or hyp_class.shape[0] != B or tuple(hyp_pose.shape) != tuple(hyp_class.shape) + (3, 4):
-        raise ValueError("hyp_class must be [B,n] and hyp_pose [B,n,3,4] (got %s, %s)" % (tuple(hyp_class.shape), tuple(hyp_pose.shape)))
-    n = hyp_class.shape[1]
-    dev = records.device
-    pose_out = torch.empty((B, n, 3, 4), dtype=torch.float64, device=dev)
-    class_out = torch.empty((B, n), dtype=torch.int32, device=dev)
-    inliers_out = torch.empty((B, n), dtype=torch.int32, device=dev)
-    check("pcnn_pose2d_round_fwd",
-          lib().pcnn_pose2d_round_fwd(_ptr(records), _ptr(counts), _ptr(offsets), _ptr(intrinsics), _ptr(hyp_pose), _ptr(hyp_class),
-                                      B, H, W, C, n, int(round), int(pixel_batch), int(max_pixels), float(inlier_threshold),
-                                      _ptr(pose_out), _ptr(class_out), _ptr(inliers_out), _stream(records)))
-    return pose_out, class_out, inliers_out
+    n, outs = _pose_round_outputs(hyp_pose, hyp_class, B)
+    call("pcnn_pose2d_round_fwd", _ptr(records), _ptr(counts), _ptr(offsets), _ptr(intrinsics), _ptr(hyp_pose), _ptr(hyp_class), B,
+         H, W, C, n, int(round), int(pixel_batch), int(max_pixels), float(inlier_threshold), *map(_ptr, outs), _stream(records))
+    return outs
 
 
 def estimate_poses_2d(label_2d, vertex_pred, extents, intrinsics, seed=0, streams=None, hypotheses=256, pixel_batch=1000,
@@ -1912,23 +1807,11 @@ def estimate_poses_2d(label_2d, vertex_pred, extents, intrinsics, seed=0, stream
     [B,C,3,4], inliers, ref_steps, num_hyps int32 [B,C]); a class without hypothesis is all zero. inlier_threshold and
     min_dist2d are in pixels, min_dist3d in metres. min_pixels only gated the reference's nlopt polish, which is not built:
     accepted and unused. Deviations from the reference: DESIGN.md 3.7c."""
-    label_2d, vertex_pred, extents, intrinsics, B, H, W, C = _pose2d_frames(label_2d, vertex_pred, extents, intrinsics)
-    dev = label_2d.device
-    streams = _pose3d_streams(streams, B, dev)
-    s0, s1 = _pose3d_seed(seed)
-    int(min_pixels)
-    nbytes = c_size_t()
-    check("pcnn_pose2d_workspace_bytes", lib().pcnn_pose2d_workspace_bytes(B, H, W, C, int(hypotheses), ctypes.byref(nbytes)))
-    ws = (workspace or _ws(dev, "pose2d")).get(nbytes.value, dev)
-    poses64 = torch.empty((B, C, 3, 4), dtype=torch.float64, device=dev)
-    poses = torch.empty((B, C, 3, 4), dtype=torch.float32, device=dev)
-    inliers = torch.empty((B, C), dtype=torch.int32, device=dev)
-    ref_steps = torch.empty((B, C), dtype=torch.int32, device=dev)
-    num_hyps = torch.empty((B, C), dtype=torch.int32, device=dev)
-    check("pcnn_pose2d_estimate_fwd",
-          lib().pcnn_pose2d_estimate_fwd(_ptr(label_2d), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics), _ptr(streams), s0, s1,
-                                         B, H, W, C, int(hypotheses), int(pixel_batch), int(max_pixels), int(ref_it), int(min_area),
-                                         float(inlier_threshold), float(min_dist2d), float(min_dist3d), int(max_attempts),
-                                         _ptr(poses64), _ptr(poses), _ptr(inliers), _ptr(ref_steps), _ptr(num_hyps), _ptr(ws),
-                                         nbytes.value, _stream(poses)))
+    label_2d, _, vertex_pred, extents, intrinsics, B, H, W, C = _pose_frames(label_2d, vertex_pred, extents, intrinsics)
+    streams, s0, s1, ws, nbytes, outs = _pose_estimate_args("pose2d", (B, H, W, C), label_2d.device, seed, streams, hypotheses,
+                                                            min_pixels, workspace)
+    call("pcnn_pose2d_estimate_fwd", _ptr(label_2d), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics), _ptr(streams), s0, s1, B,
+         H, W, C, int(hypotheses), int(pixel_batch), int(max_pixels), int(ref_it), int(min_area), float(inlier_threshold),
+         float(min_dist2d), float(min_dist3d), int(max_attempts), *map(_ptr, outs), _ptr(ws), nbytes, _stream(outs[1]))
+    poses64, poses, inliers, ref_steps, num_hyps = outs
     return poses, poses64, inliers, ref_steps, num_hyps

@@ -27,6 +27,12 @@ from .config import make_meta_data
 from .datasets import MAX_VERTEX_OBJECTS, mat2quat
 from .pose_error import quat2mat
 
+
+def call(name, *args):
+    """`_lib.call` with the handle taken from this module's `lib` (see ops.call)."""
+    check(name, getattr(lib(), name)(*args))
+
+
 MAX_INSTANCES = 32                 # PCNN_SYNTH_MAX_INSTANCES
 Z_NEAR, Z_FAR = 0.25, 6.0          # tools/train_net.py:166-167
 FACTOR_DEPTH = 1000.0              # tools/train_net.py:170
@@ -441,19 +447,15 @@ def render_scenes(bank, scenes, K, height, width, background=None, depth_range=(
     vertmap = torch.empty((S, height, width, 3), dtype=torch.float32, device=dev) if want_vertmap else None
     counts = torch.empty((N,), dtype=torch.int32, device=dev)
     valid = torch.empty((S,), dtype=torch.int32, device=dev)
-    nbytes = ctypes.c_size_t()
-    check("pcnn_synth_scene_workspace_bytes", lib().pcnn_synth_scene_workspace_bytes(S, height, width, ctypes.byref(nbytes)))
-    ws = ops._ws(dev, "synth_scene").get(nbytes.value, dev)
+    ws, nbytes = ops._workspace(dev, "synth_scene", "pcnn_synth_scene_workspace_bytes", S, height, width)
     hp = lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else ctypes.c_void_p(0)
     K = np.asarray(K, dtype=np.float64)
-    check("pcnn_synth_scene_fwd",
-          lib().pcnn_synth_scene_fwd(ops._ptr(bank.vertices), ops._ptr(bank.normals), ops._ptr(bank.colors), ops._ptr(bank.uvs),
-                                     ops._ptr(bank.faces), bank.num_vertices, bank.num_faces, hp(bank.mesh_table), len(bank),
-                                     ops._ptr(bank.textures), bank.texture_bytes, hp(bank.texture_table), hp(ids), hp(params), N,
-                                     hp(lights), ops._ptr(bg), S, height, width, float(K[0, 0]), float(K[1, 1]), float(K[0, 2]),
-                                     float(K[1, 2]), float(depth_range[0]), float(depth_range[1]), float(factor_depth), int(min_pixels),
-                                     ops._ptr(color), ops._ptr(depth), ops._ptr(label), ops._ptr(vertmap), ops._ptr(counts),
-                                     ops._ptr(valid), ops._ptr(ws), nbytes.value, ops._stream(bank.vertices)))
+    call("pcnn_synth_scene_fwd", ops._ptr(bank.vertices), ops._ptr(bank.normals), ops._ptr(bank.colors), ops._ptr(bank.uvs),
+         ops._ptr(bank.faces), bank.num_vertices, bank.num_faces, hp(bank.mesh_table), len(bank), ops._ptr(bank.textures),
+         bank.texture_bytes, hp(bank.texture_table), hp(ids), hp(params), N, hp(lights), ops._ptr(bg), S, height, width,
+         float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), float(depth_range[0]), float(depth_range[1]),
+         float(factor_depth), int(min_pixels), ops._ptr(color), ops._ptr(depth), ops._ptr(label), ops._ptr(vertmap),
+         ops._ptr(counts), ops._ptr(valid), ops._ptr(ws), nbytes, ops._stream(bank.vertices))
     return SceneBatch(bank, list(scenes), K, height, width, factor_depth, color, depth, label, vertmap, counts, valid)
 
 

@@ -1,6 +1,6 @@
-"""CPU-side checks of the drop-in boundary: libposecnn_hip.so loads without a GPU, exports every
-symbol include/posecnn_hip.h declares, and rejects bad arguments with the reference's
-InvalidArgument conditions before touching the device (no compute calls here)."""
+"""CPU-side checks of the drop-in boundary: libposecnn_hip.so loads without a GPU and rejects bad
+arguments with the reference's InvalidArgument conditions before touching the device (no compute calls
+here). That it exports and binds what the headers declare: tests/test_capi_bindings.py."""
 import ctypes
 import os
 import re
@@ -18,22 +18,6 @@ def L():
         import __graft_entry__
         __graft_entry__.build()
     return _lib.lib()
-
-
-def declared_symbols():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(pcnn_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_every_declared_symbol_is_exported_and_bound(L):
-    from posecnn_amd import _lib
-    syms = declared_symbols()
-    assert len(syms) >= 17
-    for s in syms:
-        assert hasattr(L, s), "libposecnn_hip.so does not export %s" % s
-        assert s in _lib.SIGNATURES, "posecnn_amd/_lib.py has no ctypes signature for %s" % s
-    assert sorted(_lib.SIGNATURES) == syms
 
 
 def test_abi_version_and_status_strings(L):

@@ -1,13 +1,11 @@
 """CPU-side checks of the training label head (include/posecnn_hip_loss.h, posecnn_amd/ops.label_head_loss): the float32
-log of the softmax denominator against float64 over every argument it can meet, the header against the bindings, the C
-entries' host validation, and the float32 restatement the GPU test compares with (tests/label_loss_ref.py) against float64
+log of the softmax denominator against float64 over every argument it can meet, the C entries' host validation, and the float32 restatement the GPU test compares with (tests/label_loss_ref.py) against float64
 autograd — with the five seeded defects that comparison has to turn down.
 
 Measured here and recorded in DESIGN.md: log_sum_f32 over all 50 331 649 float32 in [1, 64] is within 1.97 ulp of the
 float64 logarithm (worst at x = 1.0038618; ulp = the float32 spacing at the true value), 2.62e-7 in absolute terms."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,10 +13,7 @@ import pytest
 import grad_ref
 import label_loss_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "posecnn_hip_loss.h")
 F = np.float32
-SYMBOLS = ["pcnn_label_head_loss_bwd", "pcnn_label_head_loss_fwd", "pcnn_label_head_loss_workspace_bytes"]
 
 
 # ---- log_sum_f32 -------------------------------------------------------------------------------------------------------
@@ -44,7 +39,7 @@ def test_log_sum_f32_against_float64_over_every_float_in_range():
     assert nan[0] != nan[0]
 
 
-# ---- header and bindings -----------------------------------------------------------------------------------------------
+# ---- the C boundary ------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def L():
     from posecnn_amd import _lib
@@ -52,24 +47,6 @@ def L():
         import __graft_entry__
         __graft_entry__.build()
     return _lib.lib()
-
-
-def test_loss_header_symbols_are_bound_and_exported(L):
-    from posecnn_amd import _lib, ops
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(pcnn_[a-z0-9_]+)\s*\(", text)))
-    assert syms == SYMBOLS
-    assert sorted(_lib.LOSS_SIGNATURES) == syms
-    others = (set(_lib.SIGNATURES) | set(_lib.TRAIN_SIGNATURES) | set(_lib.FRONTEND_SIGNATURES) | set(_lib.SYNTH_SIGNATURES)
-              | set(_lib.AUGMENT_SIGNATURES))
-    assert not set(_lib.LOSS_SIGNATURES) & others
-    for s in syms:
-        fn = getattr(L, s)
-        assert fn.argtypes == _lib.LOSS_SIGNATURES[s][1] and fn.restype == _lib.LOSS_SIGNATURES[s][0]
-        decl = re.search(r"\b%s\s*\((.*?)\)" % s, text, flags=re.S).group(1)
-        assert len(decl.split(",")) == len(fn.argtypes), s
-    assert '#include "posecnn_hip.h"' in text and L.pcnn_abi_version() == 2
-    assert "label_head_loss" in ops.__all__ and "label_head_loss_grad" in ops.__all__
 
 
 def test_cpu_tensors_are_refused():

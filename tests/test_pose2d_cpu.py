@@ -308,18 +308,11 @@ def test_seeded_defects_are_caught():
 
 
 # ---- the host wrappers refuse what the header refuses, without a GPU ---------------------------------------------------------
-def test_bindings_cover_the_header():
+def test_header_constants_are_the_restatements():
     import os
     import re
-    from posecnn_amd import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     header = open(os.path.join(root, "include", "posecnn_hip_pose2d.h")).read()
-    syms = sorted(set(re.findall(r"\bint (pcnn_pose2d_\w+)\(", header)))
-    assert syms == sorted(_lib.POSE2D_SIGNATURES) and len(syms) == 5
-    assert not re.findall(r"pcnn_pose2d_", open(os.path.join(root, "include", "posecnn_hip.h")).read())   # their own header
-    for s in syms:                                                          # each prototype's argument count matches its signature
-        proto = re.search(r"\bint %s\(([^;]*)\);" % s, header).group(1)
-        assert len(proto.split(",")) == len(_lib.POSE2D_SIGNATURES[s][1]), s
     for name, value in (("RECORD", R.RECORD), ("GN_STEPS", R.GN_STEPS), ("CUBIC_STEPS", R.CUBIC_STEPS), ("POLISH_STEPS", R.POLISH_STEPS)):
         assert int(re.search(r"#define PCNN_POSE2D_%s (\d+)" % name, header).group(1)) == value
 

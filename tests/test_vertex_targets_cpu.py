@@ -1,10 +1,9 @@
 """CPU checks of the training feed's vertex targets: the numpy restatement (tests/vertex_ref.py) against recorded outputs
 of the reference's `_generate_vertex_targets` (tests/golden/vertex_targets.npz, written by
-tests/golden/make_vertex_targets_golden.py), `datasets.training_blobs` on a YCB-Video tree written here, the binding
-of include/posecnn_hip_train.h, and the host-side argument checks of its entries (nothing is launched)."""
+tests/golden/make_vertex_targets_golden.py), `datasets.training_blobs` on a YCB-Video tree written here, and the host-side argument checks of the entries of
+include/posecnn_hip_train.h (nothing is launched)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,8 +11,6 @@ import pytest
 import vertex_ref
 from posecnn_amd import config, datasets, pose_error
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "posecnn_hip_train.h")
 F = np.float32
 
 
@@ -159,19 +156,6 @@ def L():
         import __graft_entry__
         __graft_entry__.build()
     return _lib.lib()
-
-
-def test_train_header_symbols_are_bound_and_exported(L):
-    from posecnn_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(pcnn_[a-z0-9_]+)\s*\(", text)))
-    assert syms == ["pcnn_smooth_l1_vertex_gt_bwd", "pcnn_smooth_l1_vertex_gt_fwd", "pcnn_vertex_targets_fwd"]
-    assert sorted(_lib.TRAIN_SIGNATURES) == syms
-    assert not set(_lib.TRAIN_SIGNATURES) & set(_lib.SIGNATURES)
-    for s in syms:
-        fn = getattr(L, s)                                       # AttributeError: not exported
-        assert fn.argtypes == _lib.TRAIN_SIGNATURES[s][1]
-    assert '#include "posecnn_hip.h"' in text and "PCNN_ABI_VERSION" not in text
 
 
 def test_argument_validation_happens_on_the_host(L):
