@@ -102,8 +102,11 @@ def parse_headers(texts):
 
 
 def header_texts():
-    """[(basename, text)] of every include/*.h, sorted by name."""
-    return [(os.path.basename(p), open(p).read()) for p in sorted(glob.glob(os.path.join(INCLUDE_DIR, "*.h")))]
+    """[(name, text)] of every include/*.h (name: the basename), sorted, then of every include/*/*.h (name: the path under
+    include/ with forward slashes, e.g. "posecnn_hip/pose_polish.h"), sorted."""
+    top = sorted(glob.glob(os.path.join(INCLUDE_DIR, "*.h")))
+    sub = sorted(glob.glob(os.path.join(INCLUDE_DIR, "*", "*.h")))
+    return [(os.path.relpath(p, INCLUDE_DIR).replace(os.sep, "/"), open(p).read()) for p in top + sub]
 
 
 def header_abi_version(texts=None):

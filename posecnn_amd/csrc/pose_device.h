@@ -7,6 +7,7 @@
 //                    __device__ bool inlier(const double* P, const Rec& r) const;
 //                    __device__ void refit(double* P, const float* rec, int n, int m, int cnt, int max_pixels, int lane) const; };
 // Arithmetic, orders and the loop's steps are stated in the two public headers; nothing here fuses or reorders.
+// `visit_listed` is the list of the routes' final polish (pose_polish.hip, include/posecnn_hip/pose_polish.h).
 #pragma once
 #include "pcnn_device.h"
 
@@ -222,6 +223,37 @@ __device__ __forceinline__ void visit_selected(const Route& route, const double*
         sel = j < max_pixels && j * cnt / max_pixels == rk;
       }
       if (sel) visit(r);
+    }
+    seen += __popcll(mask);
+  }
+}
+
+// The polish's list (include/posecnn_hip/pose_polish.h): `visit_selected` over ALL n records of the class (m == n), telling
+// the visitor where the record stands in the list: `visit(j, r)`, j = its rank among the inliers, or the j with
+// floor(j cnt / max_pixels) == rank when the list is thinned. j < min(cnt, max_pixels). Uniform over the wave.
+template <class Route, class Visit>
+__device__ __forceinline__ void visit_listed(const Route& route, const double* P0, const float* __restrict__ rec, int n, int cnt,
+                                             int max_pixels, int lane, Visit visit)
+{
+  int seen = 0;
+  for (int k0 = 0; k0 < n; k0 += PCNN_WAVE) {
+    const int k = k0 + lane;
+    bool in = false;
+    Rec r;
+    if (k < n) {
+      r = load_rec(rec + (size_t)k * REC);
+      in = route.inlier(P0, r);
+    }
+    const unsigned long long mask = __ballot(in);
+    if (in) {
+      const long long rk = seen + __popcll(mask & lanemask_lt());
+      long long j = rk;
+      bool sel = cnt < max_pixels;
+      if (!sel) {
+        j = (rk * max_pixels + cnt - 1) / cnt;
+        sel = j < max_pixels && j * cnt / max_pixels == rk;
+      }
+      if (sel) visit((int)j, r);
     }
     seen += __popcll(mask);
   }

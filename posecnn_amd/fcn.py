@@ -218,11 +218,12 @@ def _pose_rows(poses_tmp, extents, K, num_classes):
     return rois, poses
 
 
-def poses_from_vertmap_3d(labels, im_depth, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None):
+def poses_from_vertmap_3d(labels, im_depth, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None,
+                          polish_evaluations=0):
     """The depth leg of lib/fcn/test.py:1353-1401 after the network: `Synthesizer.estimate_poses_3d` on the label map,
     the depth frame and the object-coordinate field, then one row per class with poses_tmp[2, 3, j] > 0:
     rois [n,6] = (0, class, x1, y1, x2, y2 of `_get_bb2D`), poses [n,7] = (mat2quat(R), t). The rows feed
-    `Synthesizer.icp_python(..., channel_roi=6, ...)` (:1416)."""
+    `Synthesizer.icp_python(..., channel_roi=6, ...)` (:1416). polish_evaluations > 0: with the final Nelder-Mead polish."""
     from .icp import Synthesizer
     K = np.asarray(meta_data["intrinsic_matrix"], dtype=np.float64)
     factor = float(np.asarray(meta_data["factor_depth"]).reshape(-1)[0])
@@ -230,23 +231,27 @@ def poses_from_vertmap_3d(labels, im_depth, vertex_pred, meta_data, extents, num
     extents = np.asarray(extents, dtype=np.float32)
     poses_tmp = np.zeros((3, 4, num_classes), dtype=np.float32)
     syn.estimate_poses_3d(labels, im_depth, vertex_pred, extents, poses_tmp, num_classes, K[0, 0], K[1, 1], K[0, 2], K[1, 2],
-                          factor, seed=seed)
+                          factor, seed=seed, polish_evaluations=polish_evaluations)
     return _pose_rows(poses_tmp, extents, K, num_classes)
 
 
-def poses_from_vertmap_2d(labels, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None):
+def poses_from_vertmap_2d(labels, vertex_pred, meta_data, extents, num_classes, seed=0, device="cuda", synthesizer=None,
+                          polish_evaluations=0):
     """The colour leg of lib/fcn/test.py:1362-1378 after the network: `Synthesizer.estimate_poses_2d` on the label map and
-    the object-coordinate field alone, then the rows of `poses_from_vertmap_3d`: rois_rgb [n,6], poses_rgb [n,7]."""
+    the object-coordinate field alone, then the rows of `poses_from_vertmap_3d`: rois_rgb [n,6], poses_rgb [n,7].
+    polish_evaluations > 0: with the final Nelder-Mead polish."""
     from .icp import Synthesizer
     K = np.asarray(meta_data["intrinsic_matrix"], dtype=np.float64)
     syn = synthesizer if synthesizer is not None else Synthesizer(meshes=[], device=device)
     extents = np.asarray(extents, dtype=np.float32)
     poses_tmp = np.zeros((3, 4, num_classes), dtype=np.float32)
-    syn.estimate_poses_2d(labels, vertex_pred, extents, poses_tmp, num_classes, K[0, 0], K[1, 1], K[0, 2], K[1, 2], seed=seed)
+    syn.estimate_poses_2d(labels, vertex_pred, extents, poses_tmp, num_classes, K[0, 0], K[1, 1], K[0, 2], K[1, 2], seed=seed,
+                          polish_evaluations=polish_evaluations)
     return _pose_rows(poses_tmp, extents, K, num_classes)
 
 
-def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classes, seed=0, device="cuda", rgb_poses=False):
+def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classes, seed=0, device="cuda", rgb_poses=False,
+                               polish_evaluations=0):
     """lib/fcn/test.py:1353-1401 for a `vertex_reg_3d` network (lov_color_3d.yml, linemod_*_3d.yml): the graph gives
     label_2d and the per-pixel object coordinates, `poses_from_vertmap_3d` turns them and the depth frame into poses.
     `im` BGR uint8 and `im_depth` uint16 [H,W], padded to a multiple of 16 by the caller; meta_data needs
@@ -254,7 +259,8 @@ def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classe
     poses [n,7]).
     rgb_poses=True: the colour leg (:1362-1378) instead — the last two are `poses_from_vertmap_2d`'s rois_rgb and
     poses_rgb, no depth frame enters the poses, and `im_depth` may be None for the 'COLOR' input format (meta_data then
-    needs intrinsic_matrix only)."""
+    needs intrinsic_matrix only).
+    polish_evaluations > 0: the poses go through the reference's final Nelder-Mead polish (100 evaluations there)."""
     if not getattr(net, "vertex_reg_3d", False):
         raise ValueError("im_segment_single_frame_3d needs a network built with vertex_reg_3d=True")
     if im_depth is None and not (rgb_poses and net.input_format == "COLOR"):
@@ -271,9 +277,11 @@ def im_segment_single_frame_3d(net, im, im_depth, meta_data, extents, num_classe
     g = lambda n: net.get_output(n).detach().cpu().numpy()
     labels_2d, probs, vertex_pred = g("label_2d")[0].astype(np.int32), g("prob_normalized")[0], g("vertex_pred")[0]
     if rgb_poses:
-        rois, poses = poses_from_vertmap_2d(labels_2d, vertex_pred, meta_data, extents, num_classes, seed, device)
+        rois, poses = poses_from_vertmap_2d(labels_2d, vertex_pred, meta_data, extents, num_classes, seed, device,
+                                            polish_evaluations=polish_evaluations)
     else:
-        rois, poses = poses_from_vertmap_3d(labels_2d, im_depth, vertex_pred, meta_data, extents, num_classes, seed, device)
+        rois, poses = poses_from_vertmap_3d(labels_2d, im_depth, vertex_pred, meta_data, extents, num_classes, seed, device,
+                                            polish_evaluations=polish_evaluations)
     return labels_2d, probs, vertex_pred, rois, poses
 
 

@@ -365,12 +365,14 @@ class Synthesizer:
             t = T[:, 3].astype(np.float32)
             centers[m] = (np.float32(fx) * (t[0] / t[2]) + np.float32(px), np.float32(fy) * (t[1] / t[2]) + np.float32(py))
 
-    def estimate_poses_3d(self, labels, depth, vertmap, extents, poses, num_classes, fx, fy, px, py, factor, seed=0):
+    def estimate_poses_3d(self, labels, depth, vertmap, extents, poses, num_classes, fx, fy, px, py, factor, seed=0,
+                          polish_evaluations=0, min_pixels=10):
         """`Synthesizer.estimate_poses_3d` (synthesizer.pyx:86-95 -> estimatePose3D, synthesize.cpp:1769-1966) with the
         reference's arguments: labels int32 [H,W], depth uint16 [H,W], vertmap f32 [H,W,3 num_classes] (the network's
         `vertex_pred`), extents f32 [num_classes,3]; poses f32 [3,4,num_classes] is filled in place — R|t of class j in
         poses[:, :, j], left as it was for a class without a pose (the caller reads poses[2, 3, j] > 0 as found).
-        One frame through ops.estimate_poses_3d; `seed` keys its sampler."""
+        One frame through ops.estimate_poses_3d; `seed` keys its sampler. polish_evaluations > 0 adds the reference's final
+        Nelder-Mead polish (refinementIterations = 100 there) of every class with more than min_pixels inliers."""
         from . import ops
         dev = self.device
         labels_t = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)[None]).to(dev)
@@ -378,23 +380,27 @@ class Synthesizer:
         vert_t = torch.from_numpy(np.ascontiguousarray(vertmap, dtype=np.float32)[None]).to(dev)
         ext_t = torch.from_numpy(np.ascontiguousarray(extents, dtype=np.float32).reshape(int(num_classes), 3)).to(dev)
         intr = torch.tensor([[fx, fy, px, py]], dtype=torch.float32, device=dev)
-        out, _, _, _, num_hyps = ops.estimate_poses_3d(labels_t, depth_t, vert_t, ext_t, intr, float(factor), seed=seed)
+        out, _, _, _, num_hyps = ops.estimate_poses_3d(labels_t, depth_t, vert_t, ext_t, intr, float(factor), seed=seed,
+                                                       min_pixels=min_pixels, polish_evaluations=polish_evaluations)[:5]
         out, found = out[0].cpu().numpy(), num_hyps[0].cpu().numpy() > 0
         for j in range(int(num_classes)):
             if found[j]:
                 poses[:, :, j] = out[j]
 
-    def estimate_poses_2d(self, labels, vertmap, extents, poses, num_classes, fx, fy, px, py, seed=0):
+    def estimate_poses_2d(self, labels, vertmap, extents, poses, num_classes, fx, fy, px, py, seed=0, polish_evaluations=0,
+                          min_pixels=10):
         """`Synthesizer.estimate_poses_2d` (synthesizer.pyx:75-84 -> estimatePose2D, synthesize.cpp:1571-1767) with the
         reference's arguments — `estimate_poses_3d`'s without the depth frame and its factor; poses f32 [3,4,num_classes]
-        is filled in place in the same way. One frame through ops.estimate_poses_2d; `seed` keys its sampler."""
+        is filled in place in the same way. One frame through ops.estimate_poses_2d; `seed` keys its sampler;
+        polish_evaluations and min_pixels as in `estimate_poses_3d`."""
         from . import ops
         dev = self.device
         labels_t = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)[None]).to(dev)
         vert_t = torch.from_numpy(np.ascontiguousarray(vertmap, dtype=np.float32)[None]).to(dev)
         ext_t = torch.from_numpy(np.ascontiguousarray(extents, dtype=np.float32).reshape(int(num_classes), 3)).to(dev)
         intr = torch.tensor([[fx, fy, px, py]], dtype=torch.float32, device=dev)
-        out, _, _, _, num_hyps = ops.estimate_poses_2d(labels_t, vert_t, ext_t, intr, seed=seed)
+        out, _, _, _, num_hyps = ops.estimate_poses_2d(labels_t, vert_t, ext_t, intr, seed=seed, min_pixels=min_pixels,
+                                                       polish_evaluations=polish_evaluations)[:5]
         out, found = out[0].cpu().numpy(), num_hyps[0].cpu().numpy() > 0
         for j in range(int(num_classes)):
             if found[j]:

@@ -28,6 +28,7 @@ __all__ = [
     "bias_relu_train_", "bias_relu_train_grad", "bias_relu_pool2_train", "bias_relu_pool2_train_grad",
     "estimate_poses_3d", "pose3d_prepare", "pose3d_sample", "pose3d_round",
     "estimate_poses_2d", "pose2d_prepare", "pose2d_sample", "pose2d_round",
+    "pose_polish",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -1685,18 +1686,39 @@ def _pose_round_outputs(hyp_pose, hyp_class, B):
                torch.empty((B, n), dtype=torch.int32, device=dev))
 
 
-def _pose_estimate_args(route, dims, dev, seed, streams, hypotheses, min_pixels, workspace):
+def _pose_estimate_args(route, dims, dev, seed, streams, hypotheses, min_pixels, workspace, polished_max_pixels=None):
     """What an estimate entry takes besides its frames and thresholds, `route` "pose3d" | "pose2d", dims = (B, H, W, C):
-    -> (streams, s0, s1, workspace buffer, its bytes, (poses64, poses, inliers, ref_steps, num_hyps))."""
+    -> (streams, s0, s1, workspace buffer, its bytes, (poses64, poses, inliers, ref_steps, num_hyps)).
+    polished_max_pixels (an int): the workspace of the route's polished driver instead, and the three polish outputs
+    (energy f64 [B,C,2], evals, listed int32 [B,C]) behind the five."""
     B, H, W, C = dims
     streams = _pose3d_streams(streams, B, dev)
     s0, s1 = _pose3d_seed(seed)
     int(min_pixels)
-    ws, nbytes = _workspace(dev, route, "pcnn_%s_workspace_bytes" % route, B, H, W, C, int(hypotheses), workspace=workspace)
+    if polished_max_pixels is None:
+        ws, nbytes = _workspace(dev, route, "pcnn_%s_workspace_bytes" % route, B, H, W, C, int(hypotheses), workspace=workspace)
+    else:
+        ws, nbytes = _workspace(dev, route + "_polished", "pcnn_%s_estimate_polished_workspace_bytes" % route, B, H, W, C,
+                                int(hypotheses), int(polished_max_pixels), workspace=workspace)
     outs = (torch.empty((B, C, 3, 4), dtype=torch.float64, device=dev), torch.empty((B, C, 3, 4), dtype=torch.float32, device=dev),
             torch.empty((B, C), dtype=torch.int32, device=dev), torch.empty((B, C), dtype=torch.int32, device=dev),
             torch.empty((B, C), dtype=torch.int32, device=dev))
+    if polished_max_pixels is not None:
+        outs += _pose_polish_outputs(B, C, dev)
     return streams, s0, s1, ws, nbytes, outs
+
+
+def _pose_polish_outputs(B, C, dev):
+    """(energy f64 [B,C,2], evals int32 [B,C], listed int32 [B,C]) for a polish launch to fill."""
+    return (torch.empty((B, C, 2), dtype=torch.float64, device=dev), torch.empty((B, C), dtype=torch.int32, device=dev),
+            torch.empty((B, C), dtype=torch.int32, device=dev))
+
+
+def _polish_evaluations(polish_evaluations):
+    n = int(polish_evaluations)
+    if n < 0:
+        raise ValueError("polish_evaluations must not be negative (got %d)" % n)
+    return n
 
 
 # ---- the route with a depth frame
@@ -1738,16 +1760,28 @@ def pose3d_round(records, counts, offsets, hyp_pose, hyp_class, height, width, r
 
 def estimate_poses_3d(label_2d, depth, vertex_pred, extents, intrinsics, factor_depth, seed=0, streams=None, hypotheses=256,
                       pixel_batch=1000, max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=0.01, min_dist=0.01,
-                      min_pixels=10, max_attempts=1024, workspace=None):
+                      min_pixels=10, max_attempts=1024, workspace=None, polish_evaluations=0):
     """`Synthesizer::estimatePose3D` (lib/synthesize/synthesize.cpp:1769-1966) for a batch, three launches and no
     synchronisation: label_2d int32 [B,H,W], depth uint16 [B,H,W], vertex_pred f32 [B,H,W,3C] (the `vertex_reg_3d` network's
     object coordinates, scaled into [0, 1] per extent), extents f32 [C,3], intrinsics f32 [B,4] rows (fx, fy, px, py).
     seed: the Philox key (< 2^128); streams: one uint64 id per frame (default 0), so that a frame's poses do not depend on
-    its batch slot. min_pixels only gated the reference's nlopt polish, which is not built: accepted and unused.
+    its batch slot.
     Returns device tensors (poses f32 [B,C,3,4], poses64 f64 [B,C,3,4], inliers, ref_steps, num_hyps int32 [B,C]); a class
-    without hypothesis is all zero (the reference's caller reads t_z > 0 as found). Deviations from the reference:
-    DESIGN.md 3.7b."""
+    without hypothesis is all zero (the reference's caller reads t_z > 0 as found).
+    polish_evaluations > 0 (the reference's refinementIterations is 100; 7 at least): a fourth launch, the Nelder-Mead polish
+    of `pose_polish` on every class with inliers > min_pixels (refineWithOpt, :1936-1944) — poses and poses64 are the
+    polished ones and (energy f64 [B,C,2], evals, listed int32 [B,C]) follow num_hyps. At 0, the default, there is no
+    polish and min_pixels is unused. Deviations from the reference: DESIGN.md 3.7b."""
     label_2d, depth, vertex_pred, extents, intrinsics, B, H, W, C = _pose_frames(label_2d, vertex_pred, extents, intrinsics, depth)
+    if _polish_evaluations(polish_evaluations):
+        streams, s0, s1, ws, nbytes, outs = _pose_estimate_args("pose3d", (B, H, W, C), label_2d.device, seed, streams, hypotheses,
+                                                                min_pixels, workspace, polished_max_pixels=max_pixels)
+        call("pcnn_pose3d_estimate_polished_fwd", _ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics),
+             _ptr(streams), float(factor_depth), s0, s1, B, H, W, C, int(hypotheses), int(pixel_batch), int(max_pixels), int(ref_it),
+             int(min_area), float(inlier_threshold), float(min_dist), int(max_attempts), int(min_pixels), int(polish_evaluations),
+             *map(_ptr, outs), _ptr(ws), nbytes, _stream(outs[1]))
+        poses64, poses, inliers, ref_steps, num_hyps, energy, evals, listed = outs
+        return poses, poses64, inliers, ref_steps, num_hyps, energy, evals, listed
     streams, s0, s1, ws, nbytes, outs = _pose_estimate_args("pose3d", (B, H, W, C), label_2d.device, seed, streams, hypotheses,
                                                             min_pixels, workspace)
     call("pcnn_pose3d_estimate_fwd", _ptr(label_2d), _ptr(depth), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics), _ptr(streams),
@@ -1799,15 +1833,25 @@ def pose2d_round(records, counts, offsets, intrinsics, hyp_pose, hyp_class, heig
 
 def estimate_poses_2d(label_2d, vertex_pred, extents, intrinsics, seed=0, streams=None, hypotheses=256, pixel_batch=1000,
                       max_pixels=1000, ref_it=8, min_area=400, inlier_threshold=10.0, min_dist2d=10.0, min_dist3d=0.01,
-                      min_pixels=10, max_attempts=1024, workspace=None):
+                      min_pixels=10, max_attempts=1024, workspace=None, polish_evaluations=0):
     """`Synthesizer::estimatePose2D` (lib/synthesize/synthesize.cpp:1571-1767) for a batch, three launches and no
     synchronisation, no depth frame: label_2d int32 [B,H,W], vertex_pred f32 [B,H,W,3C] (the `vertex_reg_3d` network's
     object coordinates, scaled into [0, 1] per extent), extents f32 [C,3], intrinsics f32 [B,4] rows (fx, fy, px, py).
     seed, streams and the return value as in `estimate_poses_3d`: device tensors (poses f32 [B,C,3,4], poses64 f64
     [B,C,3,4], inliers, ref_steps, num_hyps int32 [B,C]); a class without hypothesis is all zero. inlier_threshold and
-    min_dist2d are in pixels, min_dist3d in metres. min_pixels only gated the reference's nlopt polish, which is not built:
-    accepted and unused. Deviations from the reference: DESIGN.md 3.7c."""
+    min_dist2d are in pixels, min_dist3d in metres. polish_evaluations > 0: the fourth launch of `estimate_poses_3d` with
+    the reprojection energy (refineWithOpt, :1737-1745), gated by min_pixels, and (energy, evals, listed) behind num_hyps;
+    at 0, the default, no polish and min_pixels is unused. Deviations from the reference: DESIGN.md 3.7c."""
     label_2d, _, vertex_pred, extents, intrinsics, B, H, W, C = _pose_frames(label_2d, vertex_pred, extents, intrinsics)
+    if _polish_evaluations(polish_evaluations):
+        streams, s0, s1, ws, nbytes, outs = _pose_estimate_args("pose2d", (B, H, W, C), label_2d.device, seed, streams, hypotheses,
+                                                                min_pixels, workspace, polished_max_pixels=max_pixels)
+        call("pcnn_pose2d_estimate_polished_fwd", _ptr(label_2d), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics), _ptr(streams),
+             s0, s1, B, H, W, C, int(hypotheses), int(pixel_batch), int(max_pixels), int(ref_it), int(min_area),
+             float(inlier_threshold), float(min_dist2d), float(min_dist3d), int(max_attempts), int(min_pixels),
+             int(polish_evaluations), *map(_ptr, outs), _ptr(ws), nbytes, _stream(outs[1]))
+        poses64, poses, inliers, ref_steps, num_hyps, energy, evals, listed = outs
+        return poses, poses64, inliers, ref_steps, num_hyps, energy, evals, listed
     streams, s0, s1, ws, nbytes, outs = _pose_estimate_args("pose2d", (B, H, W, C), label_2d.device, seed, streams, hypotheses,
                                                             min_pixels, workspace)
     call("pcnn_pose2d_estimate_fwd", _ptr(label_2d), _ptr(vertex_pred), _ptr(extents), _ptr(intrinsics), _ptr(streams), s0, s1, B,
@@ -1815,3 +1859,45 @@ def estimate_poses_2d(label_2d, vertex_pred, extents, intrinsics, seed=0, stream
          float(min_dist2d), float(min_dist3d), int(max_attempts), *map(_ptr, outs), _ptr(ws), nbytes, _stream(outs[1]))
     poses64, poses, inliers, ref_steps, num_hyps = outs
     return poses, poses64, inliers, ref_steps, num_hyps
+
+
+# ---- the polish that ends both routes (include/posecnn_hip/pose_polish.h)
+POSE_POLISH_ROUTES = {0: 0, 1: 1, "depth": 0, "colour": 1, "color": 1}
+
+
+def pose_polish(records, counts, offsets, poses64, gate, route, intrinsics=None, *, height, width, max_pixels=1000, min_pixels=10,
+                evaluations=100, inlier_threshold=None, workspace=None):
+    """`refineWithOpt` (lib/synthesize/synthesize.cpp:1510-1567) for a batch, one launch: the Nelder-Mead polish of the
+    poses `poses64` f64 [B,C,3,4] on the records of `pose3d_prepare` (route 0 or "depth": mean point distance) or
+    `pose2d_prepare` (route 1 or "colour": mean reprojection distance, needs intrinsics f32 [B,4]). A class is polished
+    when gate[b][c] > min_pixels (gate int32 [B,C]: the `inliers` of an estimate) and the pose has an inlier among the
+    class's records under inlier_threshold (default: the route's, 0.01 m / 10 pixels); the inliers, thinned to max_pixels,
+    are the points of the energy. evaluations: exactly that many energy evaluations (7 at least; 0: nothing is polished).
+    Returns device tensors (poses f32 [B,C,3,4], poses64 f64 [B,C,3,4], energy f64 [B,C,2] (before, after), evals int32
+    [B,C], listed int32 [B,C] (the points used)); an unpolished class keeps its pose with energy, evals, listed 0. The
+    unknowns, the box and the optimiser's rules: the header; deviation from the reference: DESIGN.md 3.7b (l)."""
+    if route not in POSE_POLISH_ROUTES:
+        raise ValueError("route must be 0 / 'depth' or 1 / 'colour' (got %r)" % (route,))
+    route = POSE_POLISH_ROUTES[route]
+    H, W = int(height), int(width)
+    records, counts, offsets, B, C = _pose3d_records(records, counts, offsets, H, W)
+    poses64 = _dev(poses64, "poses64", torch.float64)
+    gate = _dev(gate, "gate", torch.int32)
+    if tuple(poses64.shape) != (B, C, 3, 4) or tuple(gate.shape) != (B, C):
+        raise ValueError("poses64 must be [%d,%d,3,4] and gate [%d,%d] (got %s, %s)" % (B, C, B, C, tuple(poses64.shape), tuple(gate.shape)))
+    if route == 1 and intrinsics is None:
+        raise ValueError("the colour route needs intrinsics")
+    if intrinsics is not None:
+        intrinsics = _dev(intrinsics, "intrinsics", torch.float32)
+        if tuple(intrinsics.shape) != (B, 4):
+            raise ValueError("intrinsics must be [%d,4] (got %s)" % (B, tuple(intrinsics.shape)))
+    thr = (POSE3D_DEFAULTS, POSE2D_DEFAULTS)[route]["inlier_threshold"] if inlier_threshold is None else inlier_threshold
+    dev = records.device
+    ws, nbytes = _workspace(dev, "pose_polish", "pcnn_pose_polish_workspace_bytes", B, C, int(max_pixels), workspace=workspace)
+    out64 = torch.empty((B, C, 3, 4), dtype=torch.float64, device=dev)
+    out32 = torch.empty((B, C, 3, 4), dtype=torch.float32, device=dev)
+    energy, evals, listed = _pose_polish_outputs(B, C, dev)
+    call("pcnn_pose_polish_fwd", route, _ptr(records), _ptr(counts), _ptr(offsets), _ptr(intrinsics), _ptr(poses64), _ptr(gate), B, H,
+         W, C, int(max_pixels), int(min_pixels), int(evaluations), float(thr), _ptr(out64), _ptr(out32), _ptr(energy), _ptr(evals),
+         _ptr(listed), _ptr(ws), nbytes, _stream(out64))
+    return out32, out64, energy, evals, listed
