@@ -598,6 +598,42 @@ int pcnn_icp_score_fwd(const float* live_vertices, const float* canonical, const
                        int32_t* hits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depth-based pose refinement, batched: Synthesizer::solveICP for every detection row of a batch of frames in one call,
+ * with no host synchronisation between its launches (legal inside a hipGraph capture on one stream).
+ *
+ * pcnn_icp_batch_fwd: labels int32 [B][H][W], depth uint16 [B][H][W], intrinsics f32 [B][4] = (fx, fy, px, py) per frame,
+ *   rois f32 [R][roi_cols] (column 0: frame index, column 1: class id), poses f32 [R][7] = (quaternion wxyz, translation),
+ *   count int32 [1] on the device = number of live rows (NULL: all R). The mesh bank is the models concatenated:
+ *   bank_vertices / bank_normals f32 [Nv][3], bank_faces int32 [Nf][3] (indices local to their model),
+ *   bank_vertex_offsets / bank_face_offsets int32 [num_classes + 1] (class id c owns [offsets[c-1], offsets[c])),
+ *   max_faces = the largest model's face count.
+ *   Per row, the steps of the per-object entries above in solveICP's order: gate (class id > 0, a model, >= min_pixels label
+ *   pixels of the class in the row's frame) -> render at the row's pose -> back-project the masked depth -> centre
+ *   (agree, pairs) -> if agree > 0: Tz = f32(sum dz) / f32(agree), t = (tx/tz Tz, ty/tz Tz, Tz) from the row's translation
+ *   (0 when tz == 0), and with polish_evaluations > 0 re-render + Nelder-Mead polish, T <- pose(x) o T -> poses_new row
+ *   -> 8 hypotheses at Tz + (0, -.02, -.01, .01, .02, .03, .04, .05) -> render + `iterations` ICP steps each, composed with
+ *   the hypothesis -> pairs > 0: SegICP hits, first maximum; else hypothesis 0 -> poses_icp row.
+ *   poses_new / poses_icp f32 [R][7]; info int32 [R][12] = (status, agree, pairs, choose, hits[8] or -1 x 8 when pairs == 0).
+ *   status: 0 dead row (at or past count), 1 refined, 2 background (class id < 1, or a frame index outside the batch),
+ *   3 under min_pixels, 4 class id without a model in the bank, 5 over the job capacity (the first max_jobs refinable rows,
+ *   in row order, are refined). Rows that are not refined are zero in both outputs and past info's first column.
+ *   The stages are the device code of the per-object entries (bit-identical to them on the same problem); the arithmetic
+ *   between them is f64 in one fixed order.   polish_evaluations: 0 (no polish) or >= 8.
+ *   workspace (pcnn_icp_batch_workspace_bytes(max_jobs, H, W), 16-byte aligned; max_jobs <= 8191), per job slot with
+ *   P = H W, each part rounded up to 256 bytes over all slots: 64 P (z-buffers of 8 poses) + 44 P (maps at the row's pose)
+ *   + 12 P (live vertex map) + P (pair mask) + 256 P (vertex and normal maps of the 8 hypotheses) + 8 * 29 * 4 ceil(P / 256)
+ *   (block sums) + 32 ceil(P / 32) (score bits) + 2224 (poses, job and diagnostics) ~ 381 P: 117 MB at 480 x 640.
+ * ------------------------------------------------------------------------------------------ */
+int pcnn_icp_batch_workspace_bytes(int max_jobs, int height, int width, size_t* bytes);
+int pcnn_icp_batch_fwd(const int32_t* labels, const uint16_t* depth, const float* intrinsics, int batch, int height,
+                       int width, float factor_depth, const float* rois, int roi_cols, const float* poses,
+                       const int32_t* count, int num_rows, const float* bank_vertices, const float* bank_normals,
+                       const int32_t* bank_faces, const int32_t* bank_vertex_offsets, const int32_t* bank_face_offsets,
+                       int num_classes, int max_faces, int max_jobs, float max_error, int iterations,
+                       int polish_evaluations, int min_pixels, float radius, float z_near, float z_far, float* poses_new,
+                       float* poses_icp, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel timing diagnostics (off by default; the reference's only instrumentation is the
  * wall-clock Timer of lib/utils/timer.py:10-32 around im_segment).
  * While enabled, every kernel launch of this library is bracketed by hipEventRecord on the launch

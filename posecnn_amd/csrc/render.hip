@@ -33,67 +33,29 @@
 #include "pcnn_device.h"
 #include "render_device.h"
 
+// The box size up to which a triangle's own thread walks it, as render_device.h defines it for every kernel that runs
+// rd_raster_body: a retune there has to be repeated here (or this file does not compile), and tests/test_thresholds_cpu.py,
+// which reads this line, then asks for the cases on either side of it to move.
+namespace render_tunables {
+constexpr int RD_SMALL = 64;
+static_assert(RD_SMALL == pcnn::RD_SMALL, "render.hip restates the tunable of render_device.h");
+}  // namespace render_tunables
+
 namespace {
 
 using namespace pcnn;
 
-constexpr int RD_SMALL = 64;     // bounding boxes up to this many pixels are walked by the triangle's own thread
-
-__device__ __forceinline__ void rd_pixel(const RdTri& t, int x, int y, int W, float znear, float zfar, unsigned tri,
-                                         unsigned long long* __restrict__ zbuf)
-{
-  float w[3], s;
-  if (!rd_weights(t, (float)x, (float)y, w, s)) return;
-  const float z = ((w[0] * t.z[0] + w[1] * t.z[1]) + w[2] * t.z[2]) / s;
-  if (!(z >= znear) || !(z <= zfar)) return;
-  const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | tri;
-  atomicMin(&zbuf[(size_t)y * W + x], key);
-}
-
 __global__ __launch_bounds__(256) void render_clear_kernel(unsigned long long* __restrict__ zbuf, long long n)
 {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) zbuf[i] = RD_EMPTY;
+  rd_clear_body(zbuf, n);
 }
 
 __global__ __launch_bounds__(256) void render_raster_kernel(
     const float* __restrict__ vtx, const int* __restrict__ faces, int nfaces, const float* __restrict__ poses, int H, int W,
     float fx, float fy, float px, float py, float znear, float zfar, unsigned long long* __restrict__ zbuf)
 {
-  __shared__ RdTri s_big[256];
-  __shared__ unsigned s_bigid[256];
-  __shared__ int s_nbig;
-  const int tid = threadIdx.x, n = blockIdx.y;
-  const int f = blockIdx.x * 256 + tid;
-  if (tid == 0) s_nbig = 0;
-  __syncthreads();
-  const float* T = poses + 12 * (size_t)n;
-  unsigned long long* zb = zbuf + (size_t)n * H * W;
-  if (f < nfaces) {
-    RdTri t;
-    float cam[3][3];
-    if (rd_setup(T, vtx, faces + 3 * (size_t)f, W, H, fx, fy, px, py, znear, t, cam)) {
-      const long long box = (long long)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1);
-      if (box <= RD_SMALL) {
-        for (int y = t.y0; y <= t.y1; y++)
-          for (int x = t.x0; x <= t.x1; x++) rd_pixel(t, x, y, W, znear, zfar, (unsigned)f, zb);
-      } else {
-        const int slot = atomicAdd(&s_nbig, 1);
-        s_big[slot] = t;
-        s_bigid[slot] = (unsigned)f;
-      }
-    }
-  }
-  __syncthreads();
-  const int nbig = s_nbig;
-  for (int q = 0; q < nbig; q++) {
-    const RdTri& t = s_big[q];
-    const int bw = t.x1 - t.x0 + 1;
-    const long long box = (long long)bw * (t.y1 - t.y0 + 1);
-    for (long long i = tid; i < box; i += 256) {
-      const int y = t.y0 + (int)(i / bw), x = t.x0 + (int)(i % bw);
-      rd_pixel(t, x, y, W, znear, zfar, s_bigid[q], zb);
-    }
-  }
+  const int n = blockIdx.y;
+  rd_raster_body(vtx, faces, nfaces, poses + 12 * (size_t)n, H, W, fx, fy, px, py, znear, zfar, zbuf + (size_t)n * H * W);
 }
 
 __global__ __launch_bounds__(256) void render_resolve_kernel(
@@ -101,57 +63,9 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(
     int H, int W, float fx, float fy, float px, float py, float znear, float canon_x_offset,
     const unsigned long long* __restrict__ zbuf, float* __restrict__ out_v, float* __restrict__ out_n, float* __restrict__ out_c)
 {
-  const long long P = (long long)H * W;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int n = blockIdx.y;
-  if (i >= P) return;
-  const unsigned long long key = zbuf[(size_t)n * P + i];
-  const float qnan = __uint_as_float(0x7fc00000u);
-  float ov[3] = {qnan, qnan, qnan}, on[3] = {qnan, qnan, qnan}, oc[3] = {qnan, qnan, qnan};
-  if (key != RD_EMPTY) {
-    const unsigned f = (unsigned)(key & 0xffffffffu);
-    const int* face = faces + 3 * (size_t)f;
-    const float* T = poses + 12 * (size_t)n;
-    RdTri t;
-    float cam[3][3], w[3], s;
-    rd_setup(T, vtx, face, W, H, fx, fy, px, py, znear, t, cam);
-    const int x = (int)(i % W), y = (int)(i / W);
-    if (rd_weights(t, (float)x, (float)y, w, s)) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) ov[k] = ((w[0] * cam[0][k] + w[1] * cam[1][k]) + w[2] * cam[2][k]) / s;
-      if (out_n) {
-        float vn[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          const float* p = nrm + 3 * (size_t)face[j];
-          const float a = p[0], b = p[1], c = p[2];
-          const float rx = (T[0] * a + T[1] * b) + T[2] * c;
-          const float ry = (T[4] * a + T[5] * b) + T[6] * c;
-          const float rz = (T[8] * a + T[9] * b) + T[10] * c;
-          const float len = sqrt_rn((rx * rx + ry * ry) + rz * rz);
-          const bool ok = len > 0.f;      // vertsAndNorms.vert: normalised only when the length is positive
-          vn[j][0] = ok ? rx / len : rx;
-          vn[j][1] = ok ? ry / len : ry;
-          vn[j][2] = ok ? rz / len : rz;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) on[k] = ((w[0] * vn[0][k] + w[1] * vn[1][k]) + w[2] * vn[2][k]) / s;
-      }
-      if (out_c) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const float a0 = vtx[3 * (size_t)face[0] + k] + (k == 0 ? canon_x_offset : 0.f);
-          const float a1 = vtx[3 * (size_t)face[1] + k] + (k == 0 ? canon_x_offset : 0.f);
-          const float a2 = vtx[3 * (size_t)face[2] + k] + (k == 0 ? canon_x_offset : 0.f);
-          oc[k] = ((w[0] * a0 + w[1] * a1) + w[2] * a2) / s;
-        }
-      }
-    }
-  }
-  const size_t o = (size_t)n * P + i;
-  if (out_v) { out_v[4 * o] = ov[0]; out_v[4 * o + 1] = ov[1]; out_v[4 * o + 2] = ov[2]; out_v[4 * o + 3] = key != RD_EMPTY ? 1.f : qnan; }
-  if (out_n) { out_n[4 * o] = on[0]; out_n[4 * o + 1] = on[1]; out_n[4 * o + 2] = on[2]; out_n[4 * o + 3] = key != RD_EMPTY ? 0.f : qnan; }
-  if (out_c) { out_c[3 * o] = oc[0]; out_c[3 * o + 1] = oc[1]; out_c[3 * o + 2] = oc[2]; }
+  const size_t o = (size_t)blockIdx.y * H * W;
+  rd_resolve_body(vtx, nrm, faces, poses + 12 * (size_t)blockIdx.y, H, W, fx, fy, px, py, znear, canon_x_offset, zbuf + o,
+                  out_v ? out_v + 4 * o : nullptr, out_n ? out_n + 4 * o : nullptr, out_c ? out_c + 3 * o : nullptr);
 }
 
 }  // namespace

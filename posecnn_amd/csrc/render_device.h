@@ -80,4 +80,121 @@ __device__ __forceinline__ bool rd_weights(const RdTri& t, float x, float y, flo
   return s > 0.f;
 }
 
+// ---- the mesh renderer's kernel bodies (render.hip: one mesh, poses in grid.y; icp_batch.hip: a job table) --------------
+constexpr int RD_SMALL = 64;     // bounding boxes up to this many pixels are walked by the triangle's own thread
+
+__device__ __forceinline__ void rd_pixel(const RdTri& t, int x, int y, int W, float znear, float zfar, unsigned tri,
+                                         unsigned long long* __restrict__ zbuf)
+{
+  float w[3], s;
+  if (!rd_weights(t, (float)x, (float)y, w, s)) return;
+  const float z = ((w[0] * t.z[0] + w[1] * t.z[1]) + w[2] * t.z[2]) / s;
+  if (!(z >= znear) || !(z <= zfar)) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | tri;
+  atomicMin(&zbuf[(size_t)y * W + x], key);
+}
+
+// n z-buffer entries to "nothing hit", grid-stride over blockIdx.x
+__device__ __forceinline__ void rd_clear_body(unsigned long long* __restrict__ zbuf, long long n)
+{
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) zbuf[i] = RD_EMPTY;
+}
+
+// One pose T f32 [12] of one mesh into its z-buffer zb [H][W]: block blockIdx.x of 256 faces
+__device__ __forceinline__ void rd_raster_body(
+    const float* __restrict__ vtx, const int* __restrict__ faces, int nfaces, const float* __restrict__ T, int H, int W,
+    float fx, float fy, float px, float py, float znear, float zfar, unsigned long long* __restrict__ zb)
+{
+  __shared__ RdTri s_big[256];
+  __shared__ unsigned s_bigid[256];
+  __shared__ int s_nbig;
+  const int tid = threadIdx.x;
+  const int f = blockIdx.x * 256 + tid;
+  if (tid == 0) s_nbig = 0;
+  __syncthreads();
+  if (f < nfaces) {
+    RdTri t;
+    float cam[3][3];
+    if (rd_setup(T, vtx, faces + 3 * (size_t)f, W, H, fx, fy, px, py, znear, t, cam)) {
+      const long long box = (long long)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1);
+      if (box <= RD_SMALL) {
+        for (int y = t.y0; y <= t.y1; y++)
+          for (int x = t.x0; x <= t.x1; x++) rd_pixel(t, x, y, W, znear, zfar, (unsigned)f, zb);
+      } else {
+        const int slot = atomicAdd(&s_nbig, 1);
+        s_big[slot] = t;
+        s_bigid[slot] = (unsigned)f;
+      }
+    }
+  }
+  __syncthreads();
+  const int nbig = s_nbig;
+  for (int q = 0; q < nbig; q++) {
+    const RdTri& t = s_big[q];
+    const int bw = t.x1 - t.x0 + 1;
+    const long long box = (long long)bw * (t.y1 - t.y0 + 1);
+    for (long long i = tid; i < box; i += 256) {
+      const int y = t.y0 + (int)(i / bw), x = t.x0 + (int)(i % bw);
+      rd_pixel(t, x, y, W, znear, zfar, s_bigid[q], zb);
+    }
+  }
+}
+
+// One pose T of one mesh: pixel blockIdx.x * 256 + threadIdx.x of its z-buffer -> its maps (each may be NULL)
+__device__ __forceinline__ void rd_resolve_body(
+    const float* __restrict__ vtx, const float* __restrict__ nrm, const int* __restrict__ faces, const float* __restrict__ T,
+    int H, int W, float fx, float fy, float px, float py, float znear, float canon_x_offset,
+    const unsigned long long* __restrict__ zbuf, float* __restrict__ out_v, float* __restrict__ out_n, float* __restrict__ out_c)
+{
+  const long long P = (long long)H * W;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  const unsigned long long key = zbuf[i];
+  const float qnan = __uint_as_float(0x7fc00000u);
+  float ov[3] = {qnan, qnan, qnan}, on[3] = {qnan, qnan, qnan}, oc[3] = {qnan, qnan, qnan};
+  if (key != RD_EMPTY) {
+    const unsigned f = (unsigned)(key & 0xffffffffu);
+    const int* face = faces + 3 * (size_t)f;
+    RdTri t;
+    float cam[3][3], w[3], s;
+    rd_setup(T, vtx, face, W, H, fx, fy, px, py, znear, t, cam);
+    const int x = (int)(i % W), y = (int)(i / W);
+    if (rd_weights(t, (float)x, (float)y, w, s)) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) ov[k] = ((w[0] * cam[0][k] + w[1] * cam[1][k]) + w[2] * cam[2][k]) / s;
+      if (out_n) {
+        float vn[3][3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          const float* p = nrm + 3 * (size_t)face[j];
+          const float a = p[0], b = p[1], c = p[2];
+          const float rx = (T[0] * a + T[1] * b) + T[2] * c;
+          const float ry = (T[4] * a + T[5] * b) + T[6] * c;
+          const float rz = (T[8] * a + T[9] * b) + T[10] * c;
+          const float len = sqrt_rn((rx * rx + ry * ry) + rz * rz);
+          const bool ok = len > 0.f;      // vertsAndNorms.vert: normalised only when the length is positive
+          vn[j][0] = ok ? rx / len : rx;
+          vn[j][1] = ok ? ry / len : ry;
+          vn[j][2] = ok ? rz / len : rz;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) on[k] = ((w[0] * vn[0][k] + w[1] * vn[1][k]) + w[2] * vn[2][k]) / s;
+      }
+      if (out_c) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const float a0 = vtx[3 * (size_t)face[0] + k] + (k == 0 ? canon_x_offset : 0.f);
+          const float a1 = vtx[3 * (size_t)face[1] + k] + (k == 0 ? canon_x_offset : 0.f);
+          const float a2 = vtx[3 * (size_t)face[2] + k] + (k == 0 ? canon_x_offset : 0.f);
+          oc[k] = ((w[0] * a0 + w[1] * a1) + w[2] * a2) / s;
+        }
+      }
+    }
+  }
+  const size_t o = (size_t)i;
+  if (out_v) { out_v[4 * o] = ov[0]; out_v[4 * o + 1] = ov[1]; out_v[4 * o + 2] = ov[2]; out_v[4 * o + 3] = key != RD_EMPTY ? 1.f : qnan; }
+  if (out_n) { out_n[4 * o] = on[0]; out_n[4 * o + 1] = on[1]; out_n[4 * o + 2] = on[2]; out_n[4 * o + 3] = key != RD_EMPTY ? 0.f : qnan; }
+  if (out_c) { out_c[3 * o] = oc[0]; out_c[3 * o + 1] = oc[1]; out_c[3 * o + 2] = oc[2]; }
+}
+
 }  // namespace pcnn

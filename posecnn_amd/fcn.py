@@ -16,7 +16,7 @@ from . import ops
 from .config import PIXEL_MEANS, make_meta_data
 
 __all__ = ["pad_im", "unpad_im", "nms", "_get_image_blob", "im_segment_single_frame",
-           "im_segment_batch", "combine_poses", "Detections", "im_segment_single_frame_3d"]
+           "im_segment_batch", "combine_poses", "Detections", "im_segment_single_frame_3d", "refine_detections"]
 
 
 def pad_im(im, factor, value=0):
@@ -391,6 +391,21 @@ def im_segment_batch(net, data, K, extents, points, symmetry, data_p=None, plant
         net.layers["loss_pose"] = ops.average_distance_loss(pred, top_target, top_weight, feed["points"],
                                                             feed["symmetry"], 0.01, num_rows=count)[0]
     return Detections(det_rows, det_count, label_2d, packed)
+
+
+def refine_detections(det, depth, intrinsics, factor_depth, synthesizer, **options):
+    """The `cfg.TEST.POSE_REFINE` leg (lib/fcn/test.py:1925-1933) for the detections of `im_segment_batch`, without a download
+    in between: det: `Detections` (its label_2d int32 [B,H,W] is the label map the refinement masks the depth with), depth
+    uint16 [B,H,W] and intrinsics f32 [B,4] = (fx, fy, px, py) on the device, synthesizer: an `icp.Synthesizer` holding the
+    models. Every row at or past det.count comes back zero. Returns `icp.RefinedBatch` (poses_new = the reference's
+    poses_refined, poses_icp, info); `options` go to `Synthesizer.icp_batch` (max_error, iterations, min_pixels, radius,
+    depth_range, max_jobs). Pass `max_jobs`: the default is one job slot per row of det.rows — its whole capacity, 336 rows at
+    B = 16 — at about 381 bytes of workspace per pixel and slot (39 GB at 480 x 640), while a frame rarely holds more than a
+    few objects; refinable rows past `max_jobs` come back with status 5."""
+    if det.label_2d is None:
+        raise ValueError("refine_detections needs the detections' label map (Detections.label_2d)")
+    rows = det.rows
+    return synthesizer.icp_batch(det.label_2d, depth, intrinsics, factor_depth, rows[:, :7], rows[:, 7:14], det.count, **options)
 
 
 def finalize_batch(det_rows, count):

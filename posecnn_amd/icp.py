@@ -17,6 +17,10 @@ class id > 0 and >= 400 label pixels, all on the GPU (gfx950 kernels of libposec
 (nlopt is absent: the polish is its published Nelder-Mead restated, the whole optimisation in one launch.) The objects of a
 frame run phase by phase on their own streams.
 
+`refine_batch` / `Synthesizer.icp_batch` run the same steps for every detection row of a BATCH of frames in one call
+(pcnn_icp_batch_fwd): a device-side job table, every stage once with a job dimension, the arithmetic between the stages on
+the device — no host round trip, so it can be captured in a graph.
+
 No assimp here: meshes are Wavefront OBJ read by `Mesh.load_obj` (positions, faces, optional normals; smooth normals are
 generated like aiProcess_GenSmoothNormals when the file has none).
 """
@@ -292,6 +296,100 @@ def refine_poses(labels, depth, K, factor_depth, rois, poses, render_fn, iterati
 HYPOTHESIS_DZ = (0.0, -0.02, -0.01, 0.01, 0.02, 0.03, 0.04, 0.05)    # synthesize.cpp:2252-2270
 
 
+# ---- the batched route: every detection row of a batch of frames in one call, no host round trip ------------------------
+INFO_COLUMNS = 12                  # info row = (status, agree, pairs, choose, hits[8])
+STATUS_DEAD, STATUS_REFINED, STATUS_BACKGROUND, STATUS_FEW_PIXELS, STATUS_NO_MODEL, STATUS_CAPACITY = range(6)
+MAX_JOBS = 8191                    # 8 hypotheses per job ride in grid.y
+
+
+class MeshBank:
+    """The `Mesh` objects of a model list concatenated on the device (class id c = meshes[c - 1]): vertices / normals f32
+    [Nv,3], faces int32 [Nf,3] (indices local to their mesh) and the per-class offset tables int32 [C + 1], so that one
+    render launch serves jobs of different classes."""
+
+    def __init__(self, meshes, device=None):
+        meshes = list(meshes)
+        dev = torch.device(device) if device is not None else (meshes[0].vertices.device if meshes else torch.device("cuda"))
+        nv = [len(m.vertices_np) for m in meshes]
+        nf = [len(m.faces_np) for m in meshes]
+        cat = lambda arrs, dt, cols: (np.concatenate(arrs) if arrs else np.zeros((0, cols))).astype(dt).reshape(-1, cols)
+        self.vertices = torch.from_numpy(cat([m.vertices_np for m in meshes], np.float32, 3)).to(dev)
+        self.normals = torch.from_numpy(cat([m.normals_np for m in meshes], np.float32, 3)).to(dev)
+        self.faces = torch.from_numpy(cat([m.faces_np for m in meshes], np.int32, 3)).to(dev)
+        self.vertex_offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(nv)]).astype(np.int32)).to(dev)
+        self.face_offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(nf)]).astype(np.int32)).to(dev)
+        self.num_classes, self.max_faces, self.device = len(meshes), max(nf) if nf else 0, self.vertices.device
+
+
+class RefinedBatch:
+    """`refine_batch`'s device tensors: poses_new f32 [R,7] (the pose with the depth-based translation and the polish),
+    poses_icp f32 [R,7] (the best refined hypothesis), info int32 [R,12] = (status, agree, pairs, choose, hits[8])."""
+
+    def __init__(self, poses_new, poses_icp, info):
+        self.poses_new, self.poses_icp, self.info = poses_new, poses_icp, info
+
+    def __iter__(self):
+        return iter((self.poses_new, self.poses_icp, self.info))
+
+
+def _batch_arg(t, name, dtype, dims, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims:
+        raise ValueError("%s must be a %d-d %s tensor" % (name, dims, str(dtype).replace("torch.", "")))
+    if not t.is_cuda or (dev is not None and t.device != dev):
+        raise ValueError("%s must live on the GPU, with the other arguments (got %s)" % (name, t.device))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def refine_batch(labels, depth, intrinsics, factor_depth, rois, poses, count, bank, max_error=ERROR_THRESHOLD, iterations=8,
+                 polish_evaluations=50, min_pixels=400, radius=0.01, depth_range=(Z_NEAR, Z_FAR), max_jobs=None, workspace=None):
+    """`solveICP` for every detection row of a batch, one call, nothing read back in between (legal inside a graph capture).
+    labels int32 [B,H,W], depth uint16 [B,H,W], intrinsics f32 [B,4] = (fx, fy, px, py) per frame, rois f32 [R,>=2] (frame
+    index, class id, ...), poses f32 [R,7] (quaternion wxyz, translation), count: device int32 holding the number of live
+    rows or None for all R — `Detections.rows[:, :7]`, `rows[:, 7:]`, `Detections.count`; bank: a `MeshBank`.
+    Each row follows `Synthesizer.icp_python`. Returns `RefinedBatch`; rows that are not refined are zero and carry their
+    status in info[:, 0]: 0 dead, 1 refined, 2 background, 3 under min_pixels, 4 no model for the class id (where
+    `icp_python` raises), 5 over `max_jobs` (default min(R, 8191); the first max_jobs refinable rows in row order are refined). A job
+    slot costs about 381 bytes per pixel of workspace — 117 MB at 480 x 640 —, so a caller whose rows are mostly dead
+    capacity (R = 336 for `im_segment_batch` at B = 16: 39 GB by default) should pass the number of objects it expects."""
+    if not isinstance(bank, MeshBank):
+        raise ValueError("bank must be an icp.MeshBank")
+    dev = bank.device
+    labels = _batch_arg(labels, "labels", torch.int32, 3, dev)
+    depth = _batch_arg(depth, "depth", torch.uint16, 3, dev)
+    intrinsics = _batch_arg(intrinsics, "intrinsics", torch.float32, 2, dev)
+    rois = _batch_arg(rois, "rois", torch.float32, 2, dev)
+    poses = _batch_arg(poses, "poses", torch.float32, 2, dev)
+    B, H, W = labels.shape
+    R = rois.shape[0]
+    if depth.shape != labels.shape or intrinsics.shape != (B, 4) or B < 1 or H < 8 or W < 8:
+        raise ValueError("labels / depth [B,H,W] with H, W >= 8 and intrinsics [B,4] (got %s, %s, %s)" % (
+            tuple(labels.shape), tuple(depth.shape), tuple(intrinsics.shape)))
+    if rois.shape[1] < 2 or poses.shape != (R, 7) or R > 65535:
+        raise ValueError("rois [R,>=2] and poses [R,7], R <= 65535 (got %s, %s)" % (tuple(rois.shape), tuple(poses.shape)))
+    if count is not None:
+        if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.numel() < 1 or count.device != dev:
+            raise ValueError("count must be a device int32 tensor (or None)")
+    if int(iterations) < 0 or 0 < int(polish_evaluations) < 8 or int(polish_evaluations) < 0:
+        raise ValueError("iterations >= 0; polish_evaluations 0 (no polish) or >= 8, the initial simplex")
+    if not (factor_depth > 0 and radius > 0 and max_error >= 0 and 0 < depth_range[0] <= depth_range[1]):
+        raise ValueError("factor_depth, radius > 0, max_error >= 0, 0 < z_near <= z_far")
+    J = min(R, MAX_JOBS) if max_jobs is None else int(max_jobs)
+    if not 0 <= J <= MAX_JOBS:
+        raise ValueError("max_jobs must lie in 0..%d (got %d)" % (MAX_JOBS, J))
+    poses_new = torch.empty((R, 7), dtype=torch.float32, device=dev)
+    poses_icp = torch.empty((R, 7), dtype=torch.float32, device=dev)
+    info = torch.empty((R, INFO_COLUMNS), dtype=torch.int32, device=dev)
+    if R == 0:
+        return RefinedBatch(poses_new, poses_icp, info)
+    ws, nbytes = ops._workspace(dev, "icp_batch", "pcnn_icp_batch_workspace_bytes", J, H, W, workspace=workspace)
+    call("pcnn_icp_batch_fwd", ops._ptr(labels), ops._ptr(depth), ops._ptr(intrinsics), B, H, W, float(factor_depth), ops._ptr(rois),
+         int(rois.shape[1]), ops._ptr(poses), ops._ptr(count), R, ops._ptr(bank.vertices), ops._ptr(bank.normals), ops._ptr(bank.faces),
+         ops._ptr(bank.vertex_offsets), ops._ptr(bank.face_offsets), bank.num_classes, bank.max_faces, J, float(max_error),
+         int(iterations), int(polish_evaluations), int(min_pixels), float(radius), float(depth_range[0]), float(depth_range[1]),
+         ops._ptr(poses_new), ops._ptr(poses_icp), ops._ptr(info), ops._ptr(ws), nbytes, ops._stream(labels))
+    return RefinedBatch(poses_new, poses_icp, info)
+
+
 class Synthesizer:
     """The slice of `libsynthesizer.Synthesizer` the test loop uses (lib/fcn/test.py:1863-1865, :1925-1933):
     `Synthesizer(model_file, pose_file)`, `setup(width, height)`, `icp_python(...)`. `model_file` lists one OBJ path per
@@ -306,6 +404,7 @@ class Synthesizer:
         self._streams = []            # one per object of a frame (created on first use)
         self.synthesis_seed = 0       # render_python: seed of the scene sampler (created on first use)
         self._bank = self._sampler = None
+        self._icp_bank = None         # icp_batch: the meshes concatenated on the device (built on first use)
 
     def setup(self, width, height):
         self.width, self.height = int(width), int(height)
@@ -405,6 +504,19 @@ class Synthesizer:
         for j in range(int(num_classes)):
             if found[j]:
                 poses[:, :, j] = out[j]
+
+    def icp_batch(self, labels, depth, intrinsics, factor_depth, rois, poses, count=None, max_error=ERROR_THRESHOLD, iterations=8,
+                  min_pixels=400, radius=0.01, depth_range=(Z_NEAR, Z_FAR), max_jobs=None):
+        """`icp_python` for every row of a batch of frames in one call, without a host round trip: `refine_batch` on this
+        synthesizer's models (concatenated into a `MeshBank` on first use) with its `polish_evaluations`. Device tensors in
+        (labels int32 [B,H,W], depth uint16 [B,H,W], intrinsics f32 [B,4], rois f32 [R,>=2], poses f32 [R,7], count int32
+        or None), `RefinedBatch` out."""
+        if self.meshes is None:
+            self.setup(labels.shape[2], labels.shape[1])
+        if self._icp_bank is None:
+            self._icp_bank = MeshBank(self.meshes, self.device)
+        return refine_batch(labels, depth, intrinsics, factor_depth, rois, poses, count, self._icp_bank, max_error, iterations,
+                            self.polish_evaluations, min_pixels, radius, depth_range, max_jobs)
 
     def icp_python(self, labelmap, depth, parameters, height, width, num_roi, channel_roi, rois, poses, outputs, outputs_icp,
                    maxError, iterations=8, min_pixels=400, radius=0.01):

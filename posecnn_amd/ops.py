@@ -28,7 +28,7 @@ __all__ = [
     "bias_relu_train_", "bias_relu_train_grad", "bias_relu_pool2_train", "bias_relu_pool2_train_grad",
     "estimate_poses_3d", "pose3d_prepare", "pose3d_sample", "pose3d_round",
     "estimate_poses_2d", "pose2d_prepare", "pose2d_sample", "pose2d_round",
-    "pose_polish",
+    "pose_polish", "icp_refine_batch",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -97,6 +97,12 @@ def _workspace(device, key, query, *dims, workspace=None, at_least=1):
     call(query, *dims, ctypes.byref(nbytes))
     need = max(nbytes.value, at_least)
     return ((workspace or _ws(device, key)).get(need, device) if need else None), nbytes.value
+
+
+def icp_refine_batch(*args, **kwargs):
+    """`icp.refine_batch` (depth-based refinement of every detection row of a batch, one call): see posecnn_amd/icp.py."""
+    from . import icp
+    return icp.refine_batch(*args, **kwargs)
 
 
 # ------------------------------------------------------------------------------------------------
