@@ -43,14 +43,13 @@ def layer(op):
             layer_input = self.inputs[0]
         else:
             layer_input = list(self.inputs)
-        if op.__name__ == "conv" and isinstance(layer_input, _RawConv) and layer_input.first is not None:
-            pass  # a Winograd conv can take a pending first conv as it is (conv() decides)
-        elif op.__name__ != "max_pool":
-            # only max_pool fuses a deferred bias + ReLU; everybody else sees the activated tensor
-            if isinstance(layer_input, list):
-                layer_input = [self._activate(i) if isinstance(i, _RawConv) else i for i in layer_input]
-            elif isinstance(layer_input, _RawConv):
-                layer_input = self._activate(layer_input)
+        # only max_pool fuses a deferred bias + ReLU, and a Winograd conv can take a pending first conv as it is (conv() decides);
+        # everybody else sees the activated tensor
+        if isinstance(layer_input, list):
+            layer_input = [i.activate(self) if isinstance(i, _Pending) else i for i in layer_input]
+        elif (isinstance(layer_input, _Pending) and op.__name__ != "max_pool"
+              and not (op.__name__ == "conv" and isinstance(layer_input, _PendingFirst))):
+            layer_input = layer_input.activate(self)
         layer_output = op(self, layer_input, *args, **kwargs)
         self.layers[name] = layer_output
         self.feed(layer_output)
@@ -127,39 +126,112 @@ def _is_raw(t):
     return isinstance(t, torch.Tensor) and t.dtype in (torch.uint8, torch.uint16)
 
 
-class _RawConv(object):
-    """A convolution output before bias + ReLU, handed to a consumer that fuses them (max_pool).
-    Fetching the layer by name materialises the activated tensor (in place) like any other."""
+class _Pending(object):
+    """A convolution output whose last step waits for its consumer: max_pool may fuse the 2x2/2 pool into that step (`pool2`),
+    everybody else, and a fetch by name, gets the activated NHWC tensor (`activate`). One subclass per form (`Network` lists
+    them); each says its `shape` (B, H, W, C) without launching anything and implements `_activate` and, if it has one, `_pool2`."""
+    def __init__(self, shape, bias, relu, out=None, pooled=None):
+        self.shape, self.bias, self.relu, self.out = shape, bias, relu, out
+        self.pooled = pooled    # the 2x2 max-pool of `out`, when the producing kernel wrote both
 
-    def __init__(self, y, bias, relu, wino=None, first=None, gemm=None, lazy12=None):
-        # y: raw NHWC conv output, or None when the conv is still pending:
-        # wino  = (M [n*n,T,C], B, H, W): in the Winograd domain, waiting for its output transform
-        # first = (x [B,H,W,3], w [3,3,3,C]): a 3-channel first conv not evaluated yet — a following
-        #         Winograd conv computes it fused with its own input transform
-        # gemm  = (V [36,T,Cin], Ut [36,Cout,Cin], B, H, W, packed): F(4x4,3x3) input transform done, the fused
-        #         GEMM + output transform kernel still to run (with or without the max-pool); packed: Ut is the fragment-major bank
-        # lazy12 = (pending conv1_1 (_RawConv with `first`), name, w): conv1_2 on top of a pending conv1_1, nothing launched
-        #         yet — a following 2x2 max_pool runs conv1_1 -> conv1_2 -> pool1 as ONE kernel; anything else that asks for the
-        #         tensor gets the unfused pair
-        self.y, self.bias, self.relu, self.out, self.wino, self.first, self.gemm = y, bias, relu, None, wino, first, gemm
-        self.lazy12 = lazy12
-        self.dual = False
-        self.pooled = None   # the 2x2 max-pool of `out`, when the producing kernel wrote both
-        self.train = None    # `y` as the framework convolution returned it ([B,C,H,W], channels_last), under fused_train_epilogue
+    def activate(self, net):   # launched once, kept in `out`
+        if self.out is None:
+            self.out = self._activate(net)
+        return self.out
 
-    @property
-    def shape(self):
-        if self.wino is not None:
-            return (self.wino[1], self.wino[2], self.wino[3], self.wino[0].shape[2])
-        if self.first is not None:
-            return tuple(self.first[0].shape[:3]) + (self.first[1].shape[3],)
-        if self.gemm is not None:
-            return (self.gemm[2], self.gemm[3], self.gemm[4], self.gemm[1].shape[-2])
-        if self.lazy12 is not None:
-            return tuple(self.lazy12[0].first[0].shape[:3]) + (self.lazy12[2].shape[0],)
-        if self.y is None and self.out is not None:
-            return tuple(self.out.shape)
-        return tuple(self.y.shape)
+    def pool2(self, net):
+        """max_pool(2, 2, 2, 2) of the activated tensor by this form's fused route, or None when it cannot fuse it here: odd H
+        or W, `out` already materialised, or a form without a fused pool."""
+        if self.pooled is None and self.out is None and self.shape[1] % 2 == 0 and self.shape[2] % 2 == 0:
+            return self._pool2(net)
+        return self.pooled
+
+    def _pool2(self, net):
+        return None
+
+
+class _PendingFirst(_Pending):
+    def __init__(self, x, w, bias, relu):
+        _Pending.__init__(self, tuple(x.shape[:3]) + (w.shape[3],), bias, relu)
+        self.x, self.w = x, w    # the frame [B,H,W,3] (f32 blob, or raw uint8 / uint16) and the filter in the TF layout [3,3,3,C]
+
+    def _activate(self, net):   # (`_conv_first` takes the torch layout and permutes it back: this view costs no copy either way)
+        return net._conv_first(raw_frame_blob(self.x), self.w.permute(3, 2, 0, 1), self.bias, self.relu)
+
+    def frames(self):   # a raw frame as the (colour, depth) pair the raw-frame kernels take: uint8 is colour, uint16 depth
+        return (self.x if self.x.dtype == torch.uint8 else None, self.x if self.x.dtype == torch.uint16 else None)
+
+    def next_v(self):
+        """V of the next layer with this conv evaluated inside its F(4x4,3x3) input transform (blobs or raw frames)."""
+        if _is_raw(self.x):
+            return ops.conv3x3_c3_winograd43_raw(*self.frames(), self.w, self.bias, self.relu)
+        return ops.conv3x3_c3_winograd43(self.x, self.w, self.bias, self.relu)
+
+
+class _PendingConv12(_Pending):
+    def __init__(self, pf, name, w, bias, relu):
+        _Pending.__init__(self, pf.shape[:3] + (w.shape[0],), bias, relu)
+        self.pf, self.name, self.w = pf, name, w    # the pending conv1_1, this layer's name and filter [C,64,3,3]
+
+    def _activate(self, net):   # somebody wants conv1_2 un-pooled: the unfused pair
+        ut, pk = net._winograd_bank(self.name, self.w)
+        return ops.winograd43_conv(self.pf.next_v(), ut, self.bias, *self.shape[:3], self.relu, pool=0, packed=pk)
+
+    def _pool2(self, net):
+        pf = self.pf
+        # the filter bank in the order the kernel's lanes consume it
+        frag = net._derived(("conv12_frag", self.name), (self.w,),
+                            lambda: ops.conv12_fragment_major(net._winograd_filter(self.name, self.w, transposed=True)),
+                            net.winograd_tile)   # (valid exactly as long as the U^T it is made of)
+        if _is_raw(pf.x):
+            return ops.conv1_1_conv1_2_fused_raw(*pf.frames(), pf.w, pf.bias, frag, self.bias, pf.relu, self.relu, ut2_layout=1)
+        return ops.conv1_1_conv1_2_fused(pf.x, pf.w, pf.bias, frag, self.bias, pf.relu, self.relu, groups=1, ut2_layout=1)
+
+
+class _PendingGemm(_Pending):
+    def __init__(self, v, ut, B, H, W, packed, bias, relu):
+        _Pending.__init__(self, (B, H, W, ut.shape[-2]), bias, relu)
+        self.v, self.ut, self.packed = v, ut, packed    # V [36,T,Cin], U^T [36,Cout,Cin] or (packed) its fragment-major bank
+
+    def _activate(self, net, pool=0):
+        return ops.winograd43_conv(self.v, self.ut, self.bias, *self.shape[:3], self.relu, pool=pool, packed=self.packed)
+
+    def _pool2(self, net):   # the same launch, writing the pooled tensor only
+        return self._activate(net, pool=1)
+
+
+class _PendingWino(_Pending):
+    def __init__(self, m, B, H, W, tile, dual, bias, relu):
+        _Pending.__init__(self, (B, H, W, m.shape[2]), bias, relu)
+        self.m, self.tile, self.dual = m, tile, dual    # M [n*n,T,C]; dual (tile 4): the max_pool writes the un-pooled tensor too
+
+    def _activate(self, net, pool=False):
+        return ops.winograd_output(self.m, self.bias, *self.shape[:3], self.relu, pool=pool, tile=self.tile)
+
+    def _pool2(self, net):
+        if not self.dual:
+            return self._activate(net, pool=True)   # a Winograd output tile is exactly one pooling window
+        self.out, pooled = ops.winograd43_output_both(self.m, self.bias, *self.shape[:3], self.relu)
+        return pooled
+
+
+class _PendingBias(_Pending):
+    def __init__(self, y, bias, relu, train=None):
+        _Pending.__init__(self, tuple(y.shape), bias, relu)
+        self.y, self.train = y, train    # raw NHWC output; train: the same as the framework returned it ([B,C,H,W], channels_last)
+
+    def _activate(self, net):
+        return net._bias_act(self.y, self.bias, self.relu)
+
+    def _pool2(self, net):
+        if self.train is not None:   # fused_train_epilogue: one byte per pooled element is all the backward keeps
+            return _nhwc(ops.bias_relu_pool2_train(self.train, self.bias, self.relu))
+        return net._bias_relu_pool2(self.y, self.bias, self.relu)
+
+
+class _ConvAndPool(_Pending):
+    def __init__(self, out, pooled, bias, relu):
+        _Pending.__init__(self, tuple(out.shape), bias, relu, out, pooled)
 
 
 class Network(object):
@@ -167,6 +239,15 @@ class Network(object):
 
     Variables live in `self.vars` under '<layer>/weights' and '<layer>/biases' (the names
     tf.variable_scope + make_var give them, network.py:169-185) and are created on first use.
+
+    `conv` may hand the next layer a `_Pending` in place of a tensor: `max_pool` takes its fused pool, all else its activated tensor.
+      _PendingFirst   a 3-channel first conv, nothing launched: a following Winograd conv evaluates it inside its own input transform
+      _PendingConv12  conv1_2 on top of a pending conv1_1, nothing launched: a following 2x2 max_pool runs conv1_1 -> conv1_2 ->
+                      pool1 as ONE kernel; anything else that asks for the tensor gets the unfused pair
+      _PendingGemm    F(4x4,3x3) input transform done, GEMM + output kernel still to run: it can write the pooled tensor instead
+      _PendingWino    Winograd domain, framework GEMM done: the output transform pools on the way out (`dual`: writes both tensors)
+      _PendingBias    the raw output of the framework convolution: bias + ReLU + 2x2 max is one pass over it, not two
+      _ConvAndPool    nothing left to do: the kernel wrote the activated tensor and its 2x2 max-pool (conv4_3 is read both ways)
     """
 
     # A training-graph switch, not an inference route: under autograd and on the GPU, bias + ReLU (+ the 2x2 max_pool) behind
@@ -238,41 +319,14 @@ class Network(object):
             raise KeyError("Unknown layer name fed: %s" % name)
         if isinstance(out, _Lazy):
             out = self.layers[name] = out.fn()
-        if isinstance(out, _RawConv):
-            out = self.layers[name] = self._activate(out)
+        if isinstance(out, _Pending):
+            out = self.layers[name] = out.activate(self)
         return out
-
-    def _activate(self, raw):
-        if raw.out is None:
-            if raw.wino is not None:
-                m, B, H, W = raw.wino
-                raw.out = ops.winograd_output(m, raw.bias, B, H, W, raw.relu, pool=False, tile=self.winograd_tile)
-            elif raw.first is not None:
-                raw.out = ops.conv3x3_c3(raw_frame_blob(raw.first[0]), raw.first[1], raw.bias, raw.relu)
-            elif raw.gemm is not None:
-                v, ut, B, H, W, pk = raw.gemm
-                raw.out = ops.winograd43_conv(v, ut, raw.bias, B, H, W, raw.relu, pool=0, packed=pk)
-            elif raw.lazy12 is not None:   # somebody wants conv1_2 un-pooled: the unfused pair
-                pf, name12, w2 = raw.lazy12
-                B, H, W = pf.shape[:3]
-                ut, pk = self._winograd_bank(name12, w2)
-                raw.out = ops.winograd43_conv(self._first_conv_v(pf), ut, raw.bias, B, H, W, raw.relu, pool=0, packed=pk)
-            else:
-                raw.out = self._bias_act(raw.y, raw.bias, raw.relu)
-        return raw.out
 
     def _conv12_fused_at(self, H, W):
         """Does the one-kernel conv1_1 -> conv1_2 -> pool1 (csrc/conv_first.hip) apply to H x W frames? The core every site
         shares; each adds its own conditions (the layer's channels, `defer_act`, the grouped trunk's preconditions)."""
         return self.fused_conv12 and self.winograd_mfma and H % 16 == 0 and W % 16 == 0
-
-    def _first_conv_v(self, pf):
-        """V of conv1_2 with the pending conv1_1 `pf` evaluated inside its input transform (blobs or raw frames)."""
-        x0 = pf.first[0]
-        if _is_raw(x0):
-            return ops.conv3x3_c3_winograd43_raw(x0 if x0.dtype == torch.uint8 else None, x0 if x0.dtype == torch.uint16 else None,
-                                                 pf.first[1], pf.bias, pf.relu)
-        return ops.conv3x3_c3_winograd43(x0, pf.first[1], pf.bias, pf.relu)
 
     def _winograd_filter(self, name, w, transposed=False):
         """U = G g G^T of a conv filter ([n*n, Cin, Cout]; transposed: [n*n, Cout, Cin] for the fused
@@ -313,38 +367,43 @@ class Network(object):
         self._cache[slot] = (tuple(sources), tuple(s._version for s in sources), extra, value)
         return value
 
-    def _winograd43_tail(self, name, v, w, b, relu, B_, H_, W_, c_i, c_o, timing):
-        """Everything after the F(4x4,3x3) input transform: the library's fp32-MFMA kernel (contractions
-        + output transform, optionally the following 2x2 max-pool) for Cin, Cout multiples of 64;
-        framework batched GEMM + output transform kernel otherwise."""
-        if self.winograd_mfma and c_i % 64 == 0 and c_o % 64 == 0:
+    def _timing(self, extra):
+        """For a route's `conv_timing` entry: (start event, recorded here; end event; `extra` flops) — None when nobody collects them."""
+        if self.conv_timing is not None:
+            timing = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), extra)
+            timing[0].record()
+            return timing
+
+    def _timed(self, name, timing, executed, direct):
+        if timing is not None:   # the end of what `_timing` started
+            timing[1].record()
+            self.conv_timing.append((name, executed + timing[2], direct + timing[2], timing[0], timing[1]))
+
+    def _conv_winograd(self, name, input, w, b, relu, c_i, c_o, tile):
+        """A 3x3 conv in the Winograd domain, of an NHWC tensor or of a pending first conv, which the input transform evaluates on
+        the fly. Behind the transform, F(4x4,3x3) with Cin, Cout multiples of 64: the library's fp32-MFMA kernel (contractions +
+        output transform, optionally the following 2x2 max-pool); else, and F(2x2,3x3): framework batched GEMM + output kernel."""
+        B_, H_, W_ = input.shape[:3]
+        first = isinstance(input, _PendingFirst)   # (its 27 products per output are timed with this layer)
+        timing = self._timing(2.0 * B_ * H_ * W_ * c_i * 27 if first else 0.0)
+        v = input.next_v() if first else ops.winograd_input(input, tile)
+        if tile == 4 and self.winograd_mfma and c_i % 64 == 0 and c_o % 64 == 0:
             ut, pk = self._winograd_bank(name, w)
-            if timing is not None:
-                timing[1].record()   # the MFMA kernel is timed by the library's own events
-                self.conv_timing.append((name, timing[2], timing[2], timing[0], timing[1]))
+            self._timed(name, timing, 0.0, 0.0)   # the MFMA kernel is timed by the library's own events
             even = H_ % 2 == 0 and W_ % 2 == 0
             if name in self.defer_act and even:
-                return _RawConv(None, b, relu, gemm=(v, ut, B_, H_, W_, pk))      # the following max_pool decides
+                return _PendingGemm(v, ut, B_, H_, W_, pk, b, relu)      # the following max_pool decides
             if name in self.dual_pool and even:
-                out = _RawConv(None, b, relu)
-                out.out, out.pooled = ops.winograd43_conv(v, ut, b, B_, H_, W_, relu, pool=2, packed=pk)
-                return out
+                return _ConvAndPool(*ops.winograd43_conv(v, ut, b, B_, H_, W_, relu, pool=2, packed=pk), b, relu)
             return ops.winograd43_conv(v, ut, b, B_, H_, W_, relu, pool=0, packed=pk)
         m = torch.bmm(v, self._winograd_filter(name, w))
-        executed = 2.0 * m.numel() * c_i
-        if timing is not None:
-            timing[1].record()   # transform + GEMMs; the output transform is timed by the library
+        # transform + GEMMs; the output transform is timed by the library
+        self._timed(name, timing, 2.0 * m.numel() * c_i, 2.0 * B_ * H_ * W_ * c_o * c_i * 9)
         if name in self.defer_act:
-            out = _RawConv(None, b, relu, wino=(m, B_, H_, W_))
-        elif name in self.dual_pool and H_ % 2 == 0 and W_ % 2 == 0:
-            out = _RawConv(None, b, relu, wino=(m, B_, H_, W_))
-            out.dual = True   # the following max_pool produces both tensors in one pass
-        else:
-            out = ops.winograd_output(m, b, B_, H_, W_, relu, pool=False, tile=4)
-        if timing is not None:
-            e0, e1, extra = timing
-            self.conv_timing.append((name, executed + extra, 2.0 * B_ * H_ * W_ * c_o * c_i * 9 + extra, e0, e1))
-        return out
+            return _PendingWino(m, B_, H_, W_, tile, False, b, relu)
+        if tile == 4 and name in self.dual_pool and H_ % 2 == 0 and W_ % 2 == 0:
+            return _PendingWino(m, B_, H_, W_, tile, True, b, relu)   # the following max_pool produces both tensors in one pass
+        return ops.winograd_output(m, b, B_, H_, W_, relu, pool=False, tile=tile)
 
     def get_unique_name(self, prefix):
         ident = sum(t.startswith(prefix) for t in self.layers) + 1
@@ -465,77 +524,57 @@ class Network(object):
         if c_i == -1:
             c_i = 3 if raw_in else input.shape[-1]
         assert c_i % group == 0 and c_o % group == 0
-        pending_first = input if isinstance(input, _RawConv) else None
         w, b = self._conv_vars(name, c_o, c_i // group, k_h, k_w, trainable, biased)
         assert s_h == 1 and s_w == 1 or padding == "VALID" or (k_h == 1 and k_w == 1), "strided SAME conv not on this path"
         pad = (k_h // 2, k_w // 2) if padding == "SAME" else 0
         if (self.fused_first_conv and b is not None and (k_h, k_w, c_i, group) == (3, 3, 3, 1) and padding == "SAME"
                 and c_o % 64 == 0 and not (torch.is_grad_enabled() and (w.requires_grad or input.requires_grad))):
-            # conv1_1: K = 27 is no GEMM; one HBM-bound kernel does conv + bias + ReLU — or, when a
-            # Winograd conv follows, that layer's input transform kernel does it on the fly
-            if self.fuse_first_conv_into_winograd and self.winograd_tile == 4 and self.winograd_min_channels and input.is_cuda:
-                return _RawConv(None, b, relu, first=(input.contiguous(), w.permute(2, 3, 1, 0).contiguous()))
-            return self._conv_first(raw_frame_blob(input), w, b, relu)
+            return self._conv_3_channels(input, w, b, relu)
         if raw_in:
             input = raw_frame_blob(input)
         wino_ok = (b is not None and (k_h, k_w, s_h, s_w, group) == (3, 3, 1, 1, 1) and padding == "SAME")
-        if pending_first is not None:
+        if isinstance(input, _PendingFirst):
             if (wino_ok and self.winograd_tile == 4 and self.winograd_min_channels
                     and c_i >= self.winograd_min_channels and c_i % 64 == 0 and c_o % 4 == 0
                     and not (torch.is_grad_enabled() and w.requires_grad)):
-                # conv1_1 -> conv1_2: the first conv is evaluated inside this layer's input transform
-                B_, H_, W_ = pending_first.shape[:3]
-                timing = None
-                if self.conv_timing is not None:
-                    timing = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), 2.0 * B_ * H_ * W_ * c_i * 27)
-                    timing[0].record()
-                if (self._conv12_fused_at(H_, W_) and name in self.defer_act and (c_i, c_o) == (64, 64)
-                        and pending_first.first[1].shape[3] == 64):
-                    # a 2x2 max_pool follows: conv1_1 -> conv1_2 -> pool1 as one LDS-resident kernel (csrc/conv_first.hip), launched
-                    # by that max_pool; the library's own events time it
-                    return _RawConv(None, b, relu, lazy12=(pending_first, name, w))
-                v = self._first_conv_v(pending_first)
-                return self._winograd43_tail(name, v, w, b, relu, B_, H_, W_, c_i, c_o, timing)
-            input = self._activate(pending_first)
+                return self._conv_on_pending_first(name, input, w, b, relu, c_i, c_o)
+            input = input.activate(self)
         if (wino_ok and input.is_cuda
                 and self.winograd_min_channels and c_i >= self.winograd_min_channels and c_i % 4 == 0 and c_o % 4 == 0
                 and (self.winograd_tile == 4 or (input.shape[1] % 2 == 0 and input.shape[2] % 2 == 0))
                 and not (torch.is_grad_enabled() and (w.requires_grad or input.requires_grad))):
-            B_, H_, W_, _ = input.shape
-            tile = self.winograd_tile
-            timing = None
-            if self.conv_timing is not None:
-                timing = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), 0.0)
-                timing[0].record()
-            v = ops.winograd_input(input, tile)
-            if tile == 4:
-                return self._winograd43_tail(name, v, w, b, relu, B_, H_, W_, c_i, c_o, timing)
-            m = torch.bmm(v, self._winograd_filter(name, w))
-            if timing is not None:
-                timing[1].record()
-                self.conv_timing.append((name, 2.0 * m.numel() * c_i, 2.0 * B_ * H_ * W_ * c_o * c_i * 9, timing[0], timing[1]))
-            if name in self.defer_act:
-                return _RawConv(None, b, relu, wino=(m, B_, H_, W_))
-            return ops.winograd_output(m, b, B_, H_, W_, relu, pool=False, tile=tile)
-        if self.conv_timing is not None and input.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            y = F.conv2d(_nchw(input), w, None, stride=(s_h, s_w), padding=pad, groups=group)
-            e1.record()
-            flops = 2.0 * y.numel() * (c_i // group) * k_h * k_w
-            self.conv_timing.append((name, flops, flops, e0, e1))
-        else:
-            y = F.conv2d(_nchw(input), w, None, stride=(s_h, s_w), padding=pad, groups=group)
+            return self._conv_winograd(name, input, w, b, relu, c_i, c_o, self.winograd_tile)
+        return self._conv_framework(name, input, w, b, relu, (s_h, s_w), pad, group)
+
+    def _conv_3_channels(self, input, w, b, relu):
+        """conv1_1: K = 27 is no GEMM; one HBM-bound kernel does conv + bias + ReLU — or, when a Winograd conv follows, that
+        layer's input transform kernel does it on the fly."""
+        if self.fuse_first_conv_into_winograd and self.winograd_tile == 4 and self.winograd_min_channels and input.is_cuda:
+            return _PendingFirst(input.contiguous(), w.permute(2, 3, 1, 0).contiguous(), b, relu)
+        return self._conv_first(raw_frame_blob(input), w, b, relu)
+
+    def _conv_on_pending_first(self, name, pf, w, b, relu, c_i, c_o):
+        """conv1_1 -> conv1_2: the first conv is evaluated inside this layer's input transform."""
+        if self._conv12_fused_at(*pf.shape[1:3]) and name in self.defer_act and (c_i, c_o) == (64, 64) and pf.w.shape[3] == 64:
+            # a 2x2 max_pool follows: conv1_1 -> conv1_2 -> pool1 as one LDS-resident kernel (csrc/conv_first.hip), launched
+            # by that max_pool; the library's own events time it
+            return _PendingConv12(pf, name, w, b, relu)
+        return self._conv_winograd(name, pf, w, b, relu, c_i, c_o, 4)
+
+    def _conv_framework(self, name, input, w, b, relu, stride, pad, group):
+        """The framework's convolution and what follows it: the training epilogue, nothing yet (`defer_act`), or bias + ReLU."""
+        timing = self._timing(0.0) if input.is_cuda else None
+        y = F.conv2d(_nchw(input), w, None, stride=stride, padding=pad, groups=group)
+        flops = 2.0 * y.numel() * (w.numel() // w.shape[0])   # (per output: input channels per group x k_h x k_w products)
+        self._timed(name, timing, flops, flops)
         if (b is not None and self.fused_train_epilogue and y.is_cuda and torch.is_grad_enabled()
                 and (y.requires_grad or b.requires_grad)):
             return self._conv_train_epilogue(name, y, b, relu)
         y = _nhwc(y)
         if b is not None and name in self.defer_act and not (torch.is_grad_enabled() and y.requires_grad):
-            return _RawConv(y, b, relu)
-        if b is None and not relu:
-            return y
+            return _PendingBias(y, b, relu)
         if b is None:
-            return F.relu_(y)
+            return F.relu_(y) if relu else y
         return self._bias_act(y, b, relu)  # bias_add + relu (network.py:181-187) in one pass, in place
 
     def _conv_train_epilogue(self, name, y, b, relu):
@@ -546,51 +585,20 @@ class Network(object):
             y = y.contiguous(memory_format=torch.channels_last)
         even = y.shape[2] % 2 == 0 and y.shape[3] % 2 == 0
         if name in self.defer_act and even:
-            out = _RawConv(_nhwc(y), b, relu)   # the following max_pool decides (ops.bias_relu_pool2_train)
-            out.train = y
-            return out
+            return _PendingBias(_nhwc(y), b, relu, train=y)   # the following max_pool decides (ops.bias_relu_pool2_train)
         if name in self.dual_pool and even and relu:
-            out = _RawConv(None, b, relu)
             act, pooled = ops.bias_relu_pool2_train(y, b, True, want_act=True)
-            out.out, out.pooled = _nhwc(act), _nhwc(pooled)
-            return out
+            return _ConvAndPool(_nhwc(act), _nhwc(pooled), b, relu)
         return _nhwc(ops.bias_relu_train_(y, b, relu))
 
     @layer
     def max_pool(self, input, k_h, k_w, s_h, s_w, name, padding=DEFAULT_PADDING):
         assert padding in ("SAME", "VALID")
-        if isinstance(input, _RawConv):
-            if input.pooled is not None and (k_h, k_w, s_h, s_w) == (2, 2, 2, 2):
-                return input.pooled   # written by the convolution's own kernel (pool = 2)
-            if (input.out is None and (k_h, k_w, s_h, s_w) == (2, 2, 2, 2)
-                    and input.shape[1] % 2 == 0 and input.shape[2] % 2 == 0):
-                if input.first is not None:
-                    return F.max_pool2d(_nchw(self._activate(input)), 2, 2).permute(0, 2, 3, 1).contiguous()
-                if input.gemm is not None:
-                    v, ut, B_, H_, W_, pk = input.gemm
-                    return ops.winograd43_conv(v, ut, input.bias, B_, H_, W_, input.relu, pool=1, packed=pk)
-                if input.lazy12 is not None:
-                    pf, name12, w2 = input.lazy12
-                    # the filter bank in the order the kernel's lanes consume it
-                    frag = self._derived(("conv12_frag", name12), (w2,),
-                                         lambda: ops.conv12_fragment_major(self._winograd_filter(name12, w2, transposed=True)),
-                                         self.winograd_tile)   # (valid exactly as long as the U^T it is made of)
-                    x0, w1 = pf.first
-                    if _is_raw(x0):
-                        return ops.conv1_1_conv1_2_fused_raw(x0 if x0.dtype == torch.uint8 else None, x0 if x0.dtype == torch.uint16 else None,
-                                                             w1, pf.bias, frag, input.bias, pf.relu, input.relu, ut2_layout=1)
-                    return ops.conv1_1_conv1_2_fused(x0, w1, pf.bias, frag, input.bias, pf.relu, input.relu, groups=1, ut2_layout=1)
-                if input.wino is not None and input.dual and self.winograd_tile == 4:
-                    m, B_, H_, W_ = input.wino
-                    input.out, pooled = ops.winograd43_output_both(m, input.bias, B_, H_, W_, input.relu)
-                    return pooled
-                if input.wino is not None:  # a Winograd output tile is exactly one pooling window
-                    m, B_, H_, W_ = input.wino
-                    return ops.winograd_output(m, input.bias, B_, H_, W_, input.relu, pool=True, tile=self.winograd_tile)
-                if input.train is not None:   # fused_train_epilogue: one byte per pooled element is all the backward keeps
-                    return _nhwc(ops.bias_relu_pool2_train(input.train, input.bias, input.relu))
-                return self._bias_relu_pool2(input.y, input.bias, input.relu)
-            input = self._activate(input)
+        if isinstance(input, _Pending):
+            pooled = input.pool2(self) if (k_h, k_w, s_h, s_w) == (2, 2, 2, 2) else None
+            if pooled is not None:
+                return pooled   # by the convolution's own kernel, or fused into its last step
+            input = input.activate(self)
         H, W = input.shape[1], input.shape[2]
         if padding == "SAME" and (H % s_h or W % s_w):
             # TF 'SAME' pads at the bottom/right with -inf; not reached after pad_im(., 16)

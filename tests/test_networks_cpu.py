@@ -182,6 +182,48 @@ def test_deferred_bias_relu_is_fused_only_into_max_pool():
     assert float(outs[True][2].min()) >= 0  # fetched by name: activated
 
 
+def test_deferred_bias_relu_meets_every_kind_of_consumer():
+    """The CPU twin of tests/test_gpu_pending_convs.py for the raw-output form: a conv in `defer_act` behind a 2x2/2 max_pool, a
+    fetch and then that max_pool, a max_pool with stride 1, a plain layer and a following 1x1 conv gives the tensors of a
+    network that defers nothing; only the first of them reaches the fused `_bias_relu_pool2`, and each activates at most once."""
+    rng = np.random.default_rng(10)
+    x = torch.from_numpy(rng.standard_normal((1, 6, 8, 5)).astype(F))
+    data = {"c": {"weights": rng.standard_normal((3, 3, 5, 4)).astype(F), "biases": rng.standard_normal(4).astype(F)},
+            "k": {"weights": rng.standard_normal((1, 1, 4, 4)).astype(F), "biases": rng.standard_normal(4).astype(F)}}
+
+    class Counting(vgg16_convs_cpu):
+        def _bias_act(self, y, bias, relu):
+            self.calls.append("act")
+            return vgg16_convs_cpu._bias_act(self, y, bias, relu)
+
+        def _bias_relu_pool2(self, y, bias, relu):
+            self.calls.append("pool2")
+            return torch.nn.functional.max_pool2d(vgg16_convs_cpu._bias_act(self, y, bias, relu).permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1).contiguous()
+
+    consumers = {
+        "pool": (lambda n: n.max_pool(2, 2, 2, 2, name="p"), ("p",), ["pool2"]),
+        "fetch_pool": (lambda n: (n.get_output("c"), n.max_pool(2, 2, 2, 2, name="p")), ("c", "p"), ["act"]),
+        "pool_stride1": (lambda n: n.max_pool(2, 2, 1, 1, name="p"), ("p",), ["act"]),
+        "relu": (lambda n: n.relu(name="r"), ("r",), ["act"]),
+        "conv1x1": (lambda n: n.conv(1, 1, 4, 1, 1, name="k"), ("k",), ["act", "act"]),
+    }
+    for tag, (consume, names, calls) in consumers.items():
+        outs = {}
+        for defer in (False, True):
+            net = Counting("COLOR", 22, 64, (1.0,), 1.0, -1.0)
+            net.defer_act = frozenset(["c"]) if defer else frozenset()
+            net.load(data)
+            net.layers, net.calls = {"x": x}, []
+            with torch.no_grad():
+                net.feed("x").conv(3, 3, 4, 1, 1, name="c", c_i=5)
+                consume(net)
+                outs[defer] = [net.get_output(n).clone() for n in names]
+            if defer:
+                assert net.calls == calls, (tag, net.calls)
+        for a, b_ in zip(outs[False], outs[True]):
+            assert torch.equal(a, b_), tag
+
+
 def test_load_keeps_depth_tower_weights_and_drops_constant_deconv_filters():
     """(a) a checkpoint that carries '<layer>_p' entries loads each tower from its own
     entry whatever the dict order; vgg16.npy-style dicts (no '_p' keys) still initialise both towers;
