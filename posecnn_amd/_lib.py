@@ -109,6 +109,13 @@ def header_texts():
     return [(os.path.relpath(p, INCLUDE_DIR).replace(os.sep, "/"), open(p).read()) for p in top + sub]
 
 
+def route_header_texts():
+    """[(name, text)] of every include/*/*/*.h (name: the path under include/), sorted: the entries of single routes of
+    the network (e.g. "posecnn_hip/trunk/conv2_fused.h"), bound like every other header, listed apart from the public ones."""
+    deep = sorted(glob.glob(os.path.join(INCLUDE_DIR, "*", "*", "*.h")))
+    return [(os.path.relpath(p, INCLUDE_DIR).replace(os.sep, "/"), open(p).read()) for p in deep]
+
+
 def header_abi_version(texts=None):
     """PCNN_ABI_VERSION as include/posecnn_hip.h defines it."""
     text = dict(header_texts() if texts is None else texts)["posecnn_hip.h"]
@@ -160,7 +167,7 @@ def lib():
         import torch  # noqa: F401
         handle = ctypes.CDLL(LIB_PATH)
         texts = header_texts()
-        bindings = parse_headers(texts)
+        bindings = parse_headers(texts + route_header_texts())
         for table in bindings.values():
             for name, (res, args) in table.items():
                 fn = getattr(handle, name)  # AttributeError if the symbol is missing: fail loudly

@@ -200,6 +200,18 @@ class _PendingGemm(_Pending):
         return self._activate(net, pool=1)
 
 
+class _PendingConv2(_Pending):
+    def __init__(self, x, utp, bias, relu):
+        _Pending.__init__(self, tuple(x.shape[:3]) + (utp.shape[-2],), bias, relu)
+        self.x, self.utp = x, utp    # the NHWC input, nothing launched, and the layer's fragment-major filter bank [36,Cout,Cin]
+
+    def _activate(self, net, pool=0):   # input transform, contractions and output transform as ONE kernel (csrc/conv2_fused.hip)
+        return ops.winograd43_conv_fused(self.x, self.utp, self.bias, self.relu, pool=pool)
+
+    def _pool2(self, net):   # the same launch, writing the pooled tensor only
+        return self._activate(net, pool=1)
+
+
 class _PendingWino(_Pending):
     def __init__(self, m, B, H, W, tile, dual, bias, relu):
         _Pending.__init__(self, (B, H, W, m.shape[2]), bias, relu)
@@ -245,6 +257,8 @@ class Network(object):
       _PendingConv12  conv1_2 on top of a pending conv1_1, nothing launched: a following 2x2 max_pool runs conv1_1 -> conv1_2 ->
                       pool1 as ONE kernel; anything else that asks for the tensor gets the unfused pair
       _PendingGemm    F(4x4,3x3) input transform done, GEMM + output kernel still to run: it can write the pooled tensor instead
+      _PendingConv2   a 64 | 128 -> 128 channel conv on the one-kernel route (`fused_conv2`), nothing launched: the following
+                      max_pool gets the pooled tensor from that kernel, everybody else the activated one
       _PendingWino    Winograd domain, framework GEMM done: the output transform pools on the way out (`dual`: writes both tensors)
       _PendingBias    the raw output of the framework convolution: bias + ReLU + 2x2 max is one pass over it, not two
       _ConvAndPool    nothing left to do: the kernel wrote the activated tensor and its 2x2 max-pool (conv4_3 is read both ways)
@@ -264,6 +278,25 @@ class Network(object):
     # bits — but a switch for A/B timing and the equality test (tests/test_gpu_wino_packed.py): set False on an instance for the
     # row-major bank through LDS.
     winograd_packed = True
+
+    # conv2_1 / conv2_2 (64 | 128 -> 128 channels) as ONE kernel each (csrc/conv2_fused.hip): input transform, contractions and
+    # output transform in a workgroup, the transformed input V never written to or read back from HBM. Bit-identical to the
+    # unfused pair wherever that pair runs its one K chain per accumulator, i.e. does not split Cin — which it never does in a
+    # launch of at least FUSED_CONV2_FLOOR blocks (wino43_cin_split, csrc/wino_mfma.hip). The route is taken for no smaller
+    # launch, so it cannot change what the network computes (tests/test_gpu_conv2_fused.py); False on an instance = the pair.
+    # `fused_conv2_min_blocks`: the least number of 16 x 16 pixel blocks in a launch for which the route is taken; values below
+    # the floor count as the floor. Measured ("conv2_1 / conv2_2 as one kernel"): the kernel wins alone from the
+    # smallest launch measured, so the default is the floor itself.
+    fused_conv2 = True
+    FUSED_CONV2_FLOOR = 128
+    fused_conv2_min_blocks = FUSED_CONV2_FLOOR
+
+    def _conv2_fused_at(self, B, H, W, c_i, c_o):
+        """Does the one-kernel route apply to a 3x3 / SAME conv of B frames of H x W with c_i -> c_o channels? The one
+        predicate of both call sites (`_conv_winograd`, `_trunk_grouped`)."""
+        return (self.fused_conv2 and self.winograd_mfma and self.winograd_tile == 4 and self.winograd_packed
+                and not (torch.is_grad_enabled() and self.trainable) and c_i in (64, 128) and c_o == 128 and H % 16 == 0 and W % 16 == 0
+                and B * (H // 16) * (W // 16) >= max(int(self.fused_conv2_min_blocks), self.FUSED_CONV2_FLOOR))
 
     def __init__(self, device="cuda", seed=3, init="he", trainable=True):
         self.inputs = []
@@ -385,6 +418,10 @@ class Network(object):
         output transform, optionally the following 2x2 max-pool); else, and F(2x2,3x3): framework batched GEMM + output kernel."""
         B_, H_, W_ = input.shape[:3]
         first = isinstance(input, _PendingFirst)   # (its 27 products per output are timed with this layer)
+        if not first and tile == 4 and self._conv2_fused_at(B_, H_, W_, c_i, c_o):
+            pc = _PendingConv2(input, self._winograd_bank(name, w)[0], b, relu)
+            self._timed(name, self._timing(0.0), 0.0, 0.0)   # an entry per layer, as on the MFMA route: the library's own events time the kernel
+            return pc if name in self.defer_act else pc.activate(self)
         timing = self._timing(2.0 * B_ * H_ * W_ * c_i * 27 if first else 0.0)
         v = input.next_v() if first else ops.winograd_input(input, tile)
         if tile == 4 and self.winograd_mfma and c_i % 64 == 0 and c_o % 64 == 0:
@@ -1064,6 +1101,13 @@ class vgg16_convs(Network):
             if li == 1:
                 v = (ops.conv3x3_c3_winograd43_raw(d, dp, packed[0][0], packed[0][1], True) if raw
                      else ops.conv3x3_c3_winograd43(x, packed[0][0], packed[0][1], True, groups=2))
+            elif self._conv2_fused_at(B2, h, w_, ci, co):
+                # conv2_1 / conv2_2 as one kernel each: V stays on the CU (csrc/conv2_fused.hip)
+                wt = self._derived(("wino_packed", "grouped", li), (va[li][0], vb[li][0]), lambda: ops.winograd43_pack_filters(wt))
+                y = ops.winograd43_conv_fused(y, wt, bias, True, pool=0 if pool is None else 1, groups=2)
+                if pool is not None:
+                    h, w_ = h // 2, w_ // 2
+                continue
             else:
                 v = ops.winograd_input(y, 4)
             # conv4_3 is read un-pooled by score_conv4 and roi_pool AND pooled by pool4: the kernel writes
@@ -1085,13 +1129,22 @@ class vgg16_convs(Network):
                     self.layers["pool4"], self.layers["pool4_p"] = y[:B], y[B:]
         return self
 
+    def _conv2_layers_fused(self, B, H, W):
+        """Do conv2_1 / conv2_2 of a step of B frames of H x W take the one-kernel route? (Towers as `_trunk_grouped` stacks them.)"""
+        towers = 2 if self.input_format == 'RGBD' and self.grouped_towers else 1
+        return self._conv2_fused_at(towers * B, H // 2, W // 2, 64, 128)
+
     def hbm_table(self, B, H, W):
         """Algorithmic HBM bytes per step of the library's streaming trunk kernels (for bench.py)."""
         towers = 2 if self.input_format == 'RGBD' else 1
         act = lambda div, ch: 4.0 * B * (H // div) * (W // div) * ch
         x_in = (act(2, 64) + act(2, 128) + act(4, 128) + 2 * act(4, 256) + act(8, 256) + 2 * act(8, 512) + 3 * act(16, 512))
         fused = self._conv12_fused_at(H, W)   # (the first two layers as one kernel)
-        t = {"wino43_input_kernel": towers * 3.25 * x_in}                             # reads X, writes V = 2.25 X
+        t = {}
+        if self._conv2_layers_fused(B, H, W):   # conv2_1 / conv2_2 read X and write Y, nothing else
+            x_in -= act(2, 64) + act(2, 128)
+            t["conv2_wino43_fused_kernel"] = towers * (act(2, 64) + act(2, 128) + act(2, 128) + act(4, 128))
+        t["wino43_input_kernel"] = towers * 3.25 * x_in                               # reads X, writes V = 2.25 X
         if not fused:
             t["conv3x3_c3_wino43_kernel"] = towers * (act(1, 3) + 2.25 * act(1, 64))      # reads the frame, writes V of conv1_2
         return t
@@ -1102,8 +1155,12 @@ class vgg16_convs(Network):
         tiles = lambda div: B * ((H // div + 3) // 4) * ((W // div + 3) // 4)
         div = {"1": 1, "2": 2, "3": 4, "4": 8, "5": 16}
         fused = self._conv12_fused_at(H, W)
-        fl = sum(2.0 * 36 * tiles(div[n[4]]) * ci * co for n, ci, co, _ in self.TRUNK if ci != 3 and not (fused and n == "conv1_2"))
+        conv2 = self._conv2_layers_fused(B, H, W)
+        fl = sum(2.0 * 36 * tiles(div[n[4]]) * ci * co for n, ci, co, _ in self.TRUNK
+                 if ci != 3 and not (fused and n == "conv1_2") and not (conv2 and n[4] == "2"))
         t = {"wino43_mfma_kernel": towers * fl}
+        if conv2:
+            t["conv2_wino43_fused_kernel"] = towers * 2.0 * 36 * tiles(2) * (64 + 128) * 128
         if fused:   # conv1_1 + conv1_2 + pool1 in one kernel: its matrix work is conv1_2's Winograd-domain contraction
             t["conv12_wino43_fused_kernel"] = towers * 2.0 * 36 * tiles(1) * 64 * 64
         return t

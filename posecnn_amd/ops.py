@@ -28,7 +28,7 @@ __all__ = [
     "bias_relu_train_", "bias_relu_train_grad", "bias_relu_pool2_train", "bias_relu_pool2_train_grad",
     "estimate_poses_3d", "pose3d_prepare", "pose3d_sample", "pose3d_round",
     "estimate_poses_2d", "pose2d_prepare", "pose2d_sample", "pose2d_round",
-    "pose_polish", "icp_refine_batch",
+    "pose_polish", "icp_refine_batch", "winograd43_conv_fused",
 ]
 
 INLIER_THRESHOLD = 0.9  # hough_voting_gpu_op.cc:356
@@ -614,6 +614,32 @@ def winograd43_conv(v, ut, bias, B, H, W, relu=True, pool=0, groups=1, packed=Fa
     call(fn, _ptr(v), _ptr(ut), _ptr(bias), B, H, W, Cin, Cout, int(groups), 1 if relu else 0, pool, _ptr(y), _ptr(yp), _ptr(ws),
          nbytes, _stream(v))
     return (y, yp) if pool == 2 else y
+
+
+def winograd43_conv_fused(x, utp, bias, relu=True, pool=0, groups=1):
+    """A 3x3 / stride 1 / SAME convolution with 64 or 128 input and 128 output channels in ONE kernel (csrc/conv2_fused.hip):
+    x [B,H,W,Cin], H and W multiples of 16; utp [groups,36,128,Cin] the bank of winograd43_pack_filters; bias [groups,128]
+    -> y [B,H,W,128] (pool=0) or its 2x2 max-pool [B,H/2,W/2,128] (pool=1). The transformed input never leaves the CU.
+    Bit-identical to winograd_input(x, 4) + winograd43_conv(..., packed=True) on the same tensors wherever that op runs one K
+    chain per accumulator: always with Cin = 64, and with Cin = 128 in every launch of at least 128 of this kernel's 16 x 16
+    pixel blocks (a smaller one the op splits over Cin when it has its workspace: two partial outputs summed afterwards,
+    another rounding order; without the workspace the entry pcnn_winograd43_conv_packed_fwd never splits)."""
+    x = _dev(x, "x", torch.float32)
+    utp = _dev(utp, "utp", torch.float32)
+    bias = _aligned16(_dev(bias, "bias", torch.float32))
+    if x.dim() != 4:
+        raise ValueError("x must be [B,H,W,Cin]")
+    B, H, W, Cin = x.shape
+    if utp.dim() == 3:
+        utp = utp.unsqueeze(0)
+    Cout = utp.shape[2]
+    if tuple(utp.shape) != (groups, 36, Cout, Cin) or bias.numel() != groups * Cout:
+        raise ValueError("utp must be [groups, 36, Cout, Cin], bias [groups, Cout]")
+    pool = int(pool)
+    y = torch.empty((B, H // 2, W // 2, Cout) if pool == 1 else (B, H, W, Cout), dtype=torch.float32, device=x.device)
+    call("pcnn_winograd43_conv_fused_fwd", _ptr(x), _ptr(utp), _ptr(bias), B, H, W, Cin, Cout, int(groups), 1 if relu else 0, pool,
+         _ptr(y), _stream(x))
+    return y
 
 
 def fc_rows(x, wt, bias, relu=True, num_rows=None, addend=None):

@@ -34,12 +34,31 @@ def timeit(fn, iters=10, warmup=3):
     return ts[len(ts) // 2]
 
 
+def conv2_rows(name, xh, u4, b, B, H, W, ci, co):
+    """conv2_1 / conv2_2: the MFMA trunk kernel on the packed bank behind the input transform, against the one kernel that keeps
+    the transformed input on the CU (csrc/conv2_fused.hip); pooled where a pool follows."""
+    pool = 1 if name == "conv2_2" else 0
+    utp = ops.winograd43_pack_filters(u4.transpose(1, 2).contiguous())
+    ms_in = timeit(lambda: ops.winograd_input(xh, 4), iters=20)
+    v4 = ops.winograd_input(xh, 4)
+    ms_mf = timeit(lambda: ops.winograd43_conv(v4, utp, b, B, H, W, True, pool, 1, packed=True), iters=20)
+    del v4
+    ms_pair = timeit(lambda: ops.winograd43_conv(ops.winograd_input(xh, 4), utp, b, B, H, W, True, pool, 1, packed=True), iters=20)
+    ms_fu = timeit(lambda: ops.winograd43_conv_fused(xh, utp, b, True, pool, 1), iters=20)
+    return {"conv2_fused_blocks": B * (H // 16) * (W // 16), "wino43_input_ms": round(ms_in, 4), "wino43_mfma_packed_ms": round(ms_mf, 4),
+            "wino43_pair_ms": round(ms_pair, 4), "conv2_fused_ms": round(ms_fu, 4),
+            "conv2_fused_TFLOPs": round(2.0 * 36 * B * (H // 4) * (W // 4) * ci * co / ms_fu / 1e9, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--layers", default="", help="comma-separated subset, e.g. conv1_2,conv2_1")
+    ap.add_argument("--conv2-fused", action="store_true",
+                    help="only conv2_1 / conv2_2 on the library's kernels: input transform, packed MFMA kernel, the pair, and the one "
+                         "fused kernel (the break-even of Network.fused_conv2_min_blocks: --batch 2 --height 256 --width 256 is 128 blocks)")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = True
     torch.backends.cudnn.allow_tf32 = False
@@ -52,6 +71,14 @@ def main():
             if a.layers and name not in a.layers.split(","):
                 continue
             H, W = a.height // div, a.width // div
+            if a.conv2_fused:
+                if name not in ("conv2_1", "conv2_2"):
+                    continue
+                xh = torch.randn((B, H, W, ci), device=dev)
+                w = torch.randn((co, ci, 3, 3), device=dev) * 0.05
+                b = torch.randn(co, device=dev)
+                res["layers"][name] = conv2_rows(name, xh, ops.winograd_filter(w, 4), b, B, H, W, ci, co)
+                continue
             x = torch.randn((B, ci, H, W), device=dev).contiguous(memory_format=torch.channels_last)
             w = torch.randn((co, ci, 3, 3), device=dev).contiguous(memory_format=torch.channels_last) * 0.05
             b = torch.randn(co, device=dev)
@@ -81,6 +108,8 @@ def main():
                                             "winograd43_gemm_ms": round(ms_mm4, 4),
                                             "winograd43_gemm_TFLOPs": round(2.0 * v4.numel() * co / ms_mm4 / 1e9, 1)})
                 del v4
+                if ci in (64, 128) and co == 128 and H % 16 == 0 and W % 16 == 0:
+                    res["layers"][name].update(conv2_rows(name, xh, u4, b, B, H, W, ci, co))
             if ci == 3:
                 xh = x.permute(0, 2, 3, 1).contiguous()
                 wh = w.permute(2, 3, 1, 0).contiguous()
@@ -94,7 +123,8 @@ def main():
                                             "fused_GBps": round(1.25 * y.numel() * 4 / ms_f / 1e6, 0)})
             tot += ms
     res["conv_total_ms"] = round(tot, 3)
-    if not a.layers:
+    res["height"], res["width"] = a.height, a.width
+    if not a.layers and not a.conv2_fused:
         res["conv_total_TFLOPs"] = round(sum(2.0 * B * (a.height // d) * (a.width // d) * ci * co * 9 for _, ci, co, d in LAYERS) / tot / 1e9, 1)
     print(json.dumps(res))
 
